@@ -7,7 +7,12 @@ already resident in HBM (torch tensor on the GPU).  One process per GPU: every
 rank demodulates its own independent channel (weak scaling, no data-path
 collective).  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n SAMPLES]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n SAMPLES] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(`value`, `ms_per_step`).  --full adds everything else to that line: the
+per-kernel profiled pass and the roofline, the single-stream pass, the
+components, the CPU baseline and the parity check.
 """
 import argparse
 import json
@@ -304,11 +309,39 @@ def parity_check(L, device, n=4 << 20):
             "gates": gates, "all_gates_pass": all(gates.values())}
 
 
+DUMP_CAP_BYTES = 60_000_000     # all files of one --dump-outputs together stay below 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """Write every array as <dirname>/<name>.npy (float32 / float64; complex as
+    (re, im) pairs).  An array over its share of DUMP_CAP_BYTES is cut to a fixed
+    sample: the elements at sorted indices drawn with seed 0, the same in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if np.iscomplexobj(a):
+            a = a.view(a.real.dtype)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, share // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the per-kernel profiled pass (kernels, stage_ms, roofline), the "
+                         "single-stream pass, the components, the CPU baseline and the parity check "
+                         "(--no-components / --no-cpu-baseline leave those two out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy: pcm (this rank's PCM block, "
+                         "float32; pcm_rank<r> for ranks above 0)")
     # (--iq-samples under torch.distributed.run, whose parser takes "--n" for a prefix of its own options)
     ap.add_argument("--n", "--iq-samples", dest="n", type=int, default=64 * 1024 * 1024)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -369,8 +402,9 @@ def main():
     radio = AMRadio(L)
     nst = len(radio.stages())
 
+    # per-stage events of the profiled pass (--full)
     events = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nst)]
-              for _ in range(args.steps)]
+              for _ in range(args.steps)] if args.full else None
     out = {}
 
     nstreams = 1 if (args.scatter and dist) else max(1, args.streams)
@@ -418,15 +452,68 @@ def main():
     # The timed steps carry HIP events around the dominant kernel's launches only (the
     # PLL walk: 2 events per step, on its launch stream, for roofline.ms_per_launch);
     # per-kernel and per-stage times come from a separate profiled pass over the same
-    # steps right after (events around every launch cost ~0.03 ms per step).
+    # steps right after (events around every launch cost ~0.03 ms per step), with --full.
+    # The timed steps are the same with and without --full, so that `value` is too.
     act0 = radio.am._walk_active()      # walker device clocks (ticks, walks) so far (synchronises)
     elapsed = timed_steps(lambda k, w: step(k, w, walk_only=kp), args.steps, args.warmup, torch.cuda.synchronize,
                           barrier)
+    y = out["y"]                        # what the last timed step returned
     act1 = radio.am._walk_active()
     host_ms = host["t"] / args.steps * 1e3
     host_max_ms = host["max"] * 1e3
     L._profile_enable(False)
     walk_timed = L._profile_report().get("k_pll_walk")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pcm" if rank == 0 else f"pcm_rank{rank}": y.cpu().numpy()})
+    if dist:
+        elapsed = reduce_max(elapsed, device)
+    n_pcm = int(y.numel())
+    value = aggregate_value(world, args.n, args.steps, elapsed)
+    res = {
+        "metric": "Msamples/s on AM chain (IIR->resample->AGC->demod), 2 MS/s IQ; HBM GB/s vs roofline",
+        "value": round(value, 3),
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": "AMRadio chain (cheby2 IIR ord8 -> resampler 48k/2M -> AGC -> AmpModem dsb+carrier "
+                               "-> de-emphasis), one independent channel per GPU",
+                   "samples_per_step_per_gpu": args.n, "iq_rate": 2000000, "pcm_rate": 48000,
+                   "pcm_samples_per_step": n_pcm,
+                   "carrier_hz": CARRIERS[(rank if args.channel is None else args.channel) % len(CARRIERS)],
+                   "seed": 4 if (rank if args.channel is None else args.channel) == 0 else 10 + (rank if args.channel is None else args.channel),
+                   "parallelism": f"channel-per-gpu x{world}" + (" rank0-scatter/gather" if args.scatter and dist else "")
+                   + (" (gloo, ranks sharing GPUs)" if dist and args.backend == "gloo" else "")},
+        "streams": nstreams,
+        "walk_early_handoff": bool(args.walk_early),
+        "host_ms_per_step": round(host_ms, 4),
+        "host_ms_max_step": round(host_max_ms, 4),
+        "kernel_events_in_timed_steps": "k_pll_walk only" if kp else False,
+        "pipeline": "each step waits for the previous step's resampler call (GPU event)" if nstreams > 1 else None,
+        "full": bool(args.full),
+    }
+    if args.full:
+        res.update(full_figures(L, args, radio, step, events, barrier, dist, device, rank, world, n_pcm,
+                                walk_timed, act0, act1))
+    if args.dump_pcm:
+        np.save(f"{args.dump_pcm}.rank{rank}.npy", y.cpu().numpy())
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    if dist:
+        tdist.destroy_process_group()
+
+
+def full_figures(L, args, radio, step, events, barrier, dist, device, rank, world, n_pcm, walk_timed, act0, act1):
+    """--full: what the line carries beside the timed steps.  The profiled pass (HIP
+    events around every launch and stage, over the same steps) and the single-stream
+    pass run right after the timed steps, on main()'s chain and step function; then
+    the components, the CPU baseline and the parity check (one GPU, rank 0 only)."""
     timed_steps(lambda k, w: step(k, w, prof=True), args.steps, 0, torch.cuda.synchronize, barrier)
     L._profile_enable(False)
     L._profile_only("")
@@ -436,14 +523,10 @@ def main():
                          barrier)
     single_steps = min(args.steps, 5)
     if dist:
-        elapsed = reduce_max(elapsed, device)
         single = reduce_max(single, device)
-    y = out["y"]
 
     stage_ms = {name: float(np.mean([events[k][i][0].elapsed_time(events[k][i][1]) for k in range(args.steps)]))
                 for i, (name, _) in enumerate(radio.stages())}
-    n_pcm = int(y.numel())
-    value = aggregate_value(world, args.n, args.steps, elapsed)
 
     # Algorithmic bytes per launch (read the stage input once, write
     # its output once; complex64 = 8 B, float32 = 4 B).  Multi-kernel stages
@@ -480,33 +563,7 @@ def main():
     achieved = alg.get(dom, 0) / (dom_ms * 1e-3) / 1e9
     entries, repairs, fallbacks = radio.am._walk_stats()       # the last call's walk (synchronises)
     res = {
-        "metric": "Msamples/s on AM chain (IIR->resample->AGC->demod), 2 MS/s IQ; HBM GB/s vs roofline",
-        "value": round(value, 3),
-        "unit": "Msamples/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": "AMRadio chain (cheby2 IIR ord8 -> resampler 48k/2M -> AGC -> AmpModem dsb+carrier "
-                               "-> de-emphasis), one independent channel per GPU",
-                   "samples_per_step_per_gpu": args.n, "iq_rate": 2000000, "pcm_rate": 48000,
-                   "pcm_samples_per_step": n_pcm,
-                   "carrier_hz": CARRIERS[(rank if args.channel is None else args.channel) % len(CARRIERS)],
-                   "seed": 4 if (rank if args.channel is None else args.channel) == 0 else 10 + (rank if args.channel is None else args.channel),
-                   "parallelism": f"channel-per-gpu x{world}" + (" rank0-scatter/gather" if args.scatter and dist else "")
-                   + (" (gloo, ranks sharing GPUs)" if dist and args.backend == "gloo" else "")},
         "roofline": dict(roofline(dom, dom_ms, achieved, entries, repairs, fallbacks), ms_source=dom_src),
-        "streams": nstreams,
-        "walk_early_handoff": bool(args.walk_early),
-        "host_ms_per_step": round(host_ms, 4),
-        "host_ms_max_step": round(host_max_ms, 4),
-        "kernel_events_in_timed_steps": "k_pll_walk only" if kp else False,
-        "pipeline": "each step waits for the previous step's resampler call (GPU event)" if nstreams > 1 else None,
         "single_stream_ms_per_step": round(single / single_steps * 1e3, 4),
         "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
         "kernels": kernels,
@@ -517,12 +574,7 @@ def main():
         res["cpu_baseline"] = cpu_baseline(args.n, args.cpu_seconds)
         res["cpu_baseline"]["host"] = host_info()
         res["parity"] = parity_check(L, device)
-    if args.dump_pcm:
-        np.save(f"{args.dump_pcm}.rank{rank}.npy", y.cpu().numpy())
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    if dist:
-        tdist.destroy_process_group()
+    return res
 
 
 def roofline(dom, dom_ms, achieved, entries, repairs, fallbacks):

@@ -5,7 +5,7 @@
 # AGC / chain tests on build_agc.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 O=gpurun_out/agcab; mkdir -p $O
-B="python3 bench.py --no-cpu-baseline --no-components --steps 20 --warmup 5"
+B="python3 bench.py --full --no-cpu-baseline --no-components --steps 20 --warmup 5"
 for r in 1 2; do
   for v in old new; do
     if [ $v = new ]; then export LDSP_PKG_DIR=$PWD/build_agc; else unset LDSP_PKG_DIR; fi

@@ -11,10 +11,10 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 rc=$?; echo "pytest gpu rc=$rc"; tail -1 $o/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -1 $o/smoke.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-components > $o/bench20.log 2>&1
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-components > $o/bench20.log 2>&1
 rc=$?; echo "bench20 rc=$rc"; [ $rc -eq 0 ] || { tail -5 $o/bench20.log; exit $rc; }
 grep '^{' $o/bench20.log | tail -1 > $o/bench_steps20.json; cut -c1-300 $o/bench_steps20.json
-timeout -k 10 700 python bench.py > $o/bench_full.log 2>&1
+timeout -k 10 700 python bench.py --full > $o/bench_full.log 2>&1
 rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || { tail -5 $o/bench_full.log; exit $rc; }
 grep '^{' $o/bench_full.log | tail -1 > $o/bench.json; cut -c1-300 $o/bench.json
 timeout -k 10 300 python scripts/chains_bench.py > $o/chains.log 2>&1 && grep '^{' $o/chains.log | tail -1 > $o/chains.json

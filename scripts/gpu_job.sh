@@ -30,7 +30,7 @@ tag=$1; shift
 o=gpurun_out/$tag
 mkdir -p "$o"
 export TMPDIR=/tmp
-B="python -u bench.py --no-cpu-baseline --no-components"
+B="python -u bench.py --full --no-cpu-baseline --no-components"
 run() {   # step name, seconds, command...
   local name=$1 secs=$2; shift 2
   timeout -k 10 "$secs" "$@" > "$o/$name.log" 2>&1
@@ -47,8 +47,8 @@ for step in "$@"; do
     b20) run b20 400 $B --steps 20 --warmup 5 ;;
     b20nk) run b20nk 400 $B --steps 20 --warmup 5 --no-kprof ;;
     b100) run b100 400 $B --steps 100 ;;
-    bench) run bench 900 python -u bench.py ;;
-    bench20) run bench20 900 python -u bench.py --steps 20 --warmup 5 ;;
+    bench) run bench 900 python -u bench.py --full ;;
+    bench20) run bench20 900 python -u bench.py --full --steps 20 --warmup 5 ;;
     pmccopy) cp "gpurun_out/prof/$tag/summary.json" "profiles/${tag}_pmc_summary.json" && echo "[pmccopy] profiles/${tag}_pmc_summary.json" ;;
     tl20|tl20:*) kv=${step#tl20}; kv=${kv#:}; name="tl20$(echo "_$kv" | tr ',=' '_-')"; rm -f "$o/$name.txt"
           env $(echo "$kv" | tr ',' ' ') LDSP_PKG_DIR=build_tuning LDSP_PROF_TIMELINE="$o/$name.txt" \
@@ -88,7 +88,7 @@ for step in "$@"; do
            grep -o '"single_stream_ms_per_step": [0-9.]*\|"k_agc_chunks": {[^}]*}\|"k_agc_runfix": {[^}]*}\|"k_pll_cand": {[^}]*}' "$o/$name.log" | tr '\n' ' '; echo
            [ $rc -eq 0 ] || { tail -15 "$o/$name.log"; exit $rc; } ;;
     tb:*) kv=${step#tb:}; name="tb_$(echo "$kv" | tr ',=' '_-')"
-          env $(echo "$kv" | tr ',' ' ') LDSP_PKG_DIR=${TB_PKG:-build_tuning} timeout -k 10 900 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$o/$name.log" 2>&1
+          env $(echo "$kv" | tr ',' ' ') LDSP_PKG_DIR=${TB_PKG:-build_tuning} timeout -k 10 900 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$o/$name.log" 2>&1
           rc=$?; echo "[$name] rc=$rc"; grep -o '"ms_per_step": [0-9.]*\|"channels_per_gpu[a-z_0-9]*": {[^}]*}' "$o/$name.log" | cut -c1-200
           [ $rc -eq 0 ] || { tail -15 "$o/$name.log"; exit $rc; } ;;
     pb:*) pk=${step#pb:}; LDSP_PKG_DIR=$pk run "pb_$(basename "$pk")" 300 python -u scripts/batched_run.py ;;

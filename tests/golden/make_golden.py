@@ -1,4 +1,4 @@
-"""Generate the golden vectors in tests/golden/golden.npz from the CPU
+"""Generate the golden vectors in tests/golden/golden.npz (and golden_chain_x.npy) from the CPU
 restatement (oracle/), which scipy/numpy pin in tests/test_oracle_*.py.
 
 The reference repository (colbyAtCRI/python-liquiddsp) holds no tests,
@@ -126,6 +126,8 @@ def main():
                               "are its intermediate stages (AGC unlocked, scale 0.01; AmpModem(0.5, dsb, carrier) and "
                               "AmpModem(0.75, dsb, costas))")
 
+    # the chain's 65536-sample input goes to a file of its own, so that each fixture stays below 1 MiB
+    np.save(os.path.join(HERE, "golden_chain_x.npy"), g.pop("chain_x"))
     np.savez(os.path.join(HERE, "golden.npz"), **g)
     with open(os.path.join(HERE, "golden.json"), "w") as fh:
         json.dump(meta, fh, indent=1)

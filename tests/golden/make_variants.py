@@ -58,7 +58,7 @@ def stage_outputs(M, g):
 
 
 def main():
-    g = dict(np.load(os.path.join(HERE, "golden.npz")))
+    g = dict(np.load(os.path.join(HERE, "golden.npz")), chain_x=np.load(os.path.join(HERE, "golden_chain_x.npy")))
     fix, meta = {}, {"generator": "tests/golden/make_variants.py",
                      "variants": {"default": "fdlibm transcendentals, portable dotprod order (= GPU exact mode)",
                                   "libm": "system libm (glibc) in the feedback loops",

@@ -19,7 +19,8 @@ import pytest
 from conftest import maxrel
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-G = np.load(os.path.join(HERE, "golden", "golden.npz"))
+G = dict(np.load(os.path.join(HERE, "golden", "golden.npz")),
+         chain_x=np.load(os.path.join(HERE, "golden", "golden_chain_x.npy")))   # (a file of its own, for size)
 
 
 def bits(a):

@@ -26,7 +26,8 @@ from conftest import maxrel
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-G = np.load(os.path.join(HERE, "golden", "golden.npz"))
+G = dict(np.load(os.path.join(HERE, "golden", "golden.npz")),
+         chain_x=np.load(os.path.join(HERE, "golden", "golden_chain_x.npy")))   # (a file of its own, for size)
 V = np.load(os.path.join(HERE, "golden", "variants.npz"))
 META = json.load(open(os.path.join(HERE, "golden", "variants.json")))
 NAMES = list(META["variants"])

@@ -14,7 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 
 V = np.load(os.path.join(HERE, "golden", "variants.npz"))
-G = np.load(os.path.join(HERE, "golden", "golden.npz"))
+G = dict(np.load(os.path.join(HERE, "golden", "golden.npz")),
+         chain_x=np.load(os.path.join(HERE, "golden", "golden_chain_x.npy")))   # (a file of its own, for size)
 META = json.load(open(os.path.join(HERE, "golden", "variants.json")))
 
 
