@@ -118,11 +118,16 @@ int ldsp_firfilt_set_scale(ldsp_firfilt_t q, float scale);
 int ldsp_firfilt_get_scale(ldsp_firfilt_t q, float *scale);
 int ldsp_firfilt_get_length(ldsp_firfilt_t q, unsigned int *n);
 int ldsp_firfilt_get_taps(ldsp_firfilt_t q, float *h);
-/* mode: LDSP_MODE_FAST (default; complex data with 48 <= L <= 1025 taps uses
+/* mode: LDSP_MODE_FAST (default; complex data with 48 <= L <= 513 taps uses
  * overlap-save FFT convolution, HBM-bound), LDSP_MODE_DIRECT (register-blocked
  * direct form), LDSP_MODE_EXACT (liquid dot-product order, bit-identical). */
 int ldsp_firfilt_set_mode(ldsp_firfilt_t q, int mode);
 int ldsp_firfilt_get_mode(ldsp_firfilt_t q, int *mode);
+/* Test hook, host logic only (works without a GPU): the kernel the next call of
+ * n samples runs -- 0 direct form, 1 overlap-save FFT, 2 exact -- and, for the
+ * FFT, its window length (512 / 1024 points) and the overlap P (history samples
+ * per window, a multiple of 64; the hop is points - P).  Pointers may be NULL. */
+int ldsp_debug_fir_dispatch(ldsp_firfilt_t q, size_t n, int *kernel, int *points, int *overlap);
 /* firfilt_*_freqresponse (firfilter.hpp:23-27) */
 int ldsp_firfilt_freqresponse(ldsp_firfilt_t q, float f, float *re, float *im);
 /* firfilt_*_execute_block (firfilter.hpp:29-35): y[i] = scale * sum_k h[k] x[i-k] */
@@ -155,6 +160,12 @@ int ldsp_resamp_get_taps(ldsp_resamp_t q, float *h, unsigned int cap, unsigned i
 int ldsp_resamp_num_outputs(ldsp_resamp_t q, size_t n, size_t *nout);
 int ldsp_resamp_execute(ldsp_resamp_t q, const void *x, size_t n, void *y, size_t cap, size_t *nout,
                         int mem, void *stream);
+/* Test hook, host logic only (works without a GPU): the kernel the next call of
+ * n samples runs at the current phase -- 0 tile (taps and span in LDS), 1 direct
+ * (branch table in LDS, windows from global memory), 2 staged (span in LDS, taps
+ * from global memory; also every call without outputs) -- and its outputs per
+ * workgroup.  Pointers may be NULL. */
+int ldsp_debug_resamp_dispatch(ldsp_resamp_t q, size_t n, int *kernel, int *outputs_per_group);
 
 /* ------------------------------------------------------------------------
  * NCO: nco_crcf (type 0 = LIQUID_NCO table, 1 = LIQUID_VCO).  Replaces NCO
@@ -231,6 +242,17 @@ int ldsp_debug_iir_path(ldsp_iirfilt_t q, int path);
  * all.  NULL turns it off.  Not thread-safe; for timing studies. */
 int ldsp_debug_iir_sect_trace(void *dev_buf);
 int ldsp_debug_iir_modal_info(ldsp_iirfilt_t q, int *ok, int *modes, int *lookback, double *err);
+/* Test hook, host logic only (works without a GPU): what a call of n samples
+ * runs with the current mode and forced path.  path: 0 speculative exact chunks,
+ * 1 sequential exact, 2 modal scan, 3 blocked scan (D <= 8), 4 chunked scan.
+ * sect_tile: on the sequential path, the tile of k_iir_sect (512 / 1024) or 0
+ * for k_iir_seq.  size_class: the unroll class (2, 4 or 17 sections /
+ * coefficients) of k_iir_seq and of the speculative kernels.  spec_W: the
+ * filter's warm-up length (0: it does not forget its state within 4096
+ * samples).  spec_staged: 1 when the speculative chunk kernel stages its input
+ * window in LDS.  Pointers may be NULL. */
+int ldsp_debug_iir_dispatch(ldsp_iirfilt_t q, size_t n, int *path, int *sect_tile, int *size_class, int *spec_W,
+                            int *spec_staged);
 int ldsp_iirfilt_destroy(ldsp_iirfilt_t q);
 int ldsp_iirfilt_reset(ldsp_iirfilt_t q);
 int ldsp_iirfilt_set_mode(ldsp_iirfilt_t q, int mode);

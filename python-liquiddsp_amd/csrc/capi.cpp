@@ -327,15 +327,22 @@ struct FirObj {
     StreamMark ord;                   // cross-stream call order (ldsp_common.hpp)
     Staging stg;
     size_t esz() const { return cplx ? 8 : 4; }
-    // FAST on complex data with L in [kFirFftMinTaps, 1025] runs the overlap-save
-    // FFT kernel (HBM-bound); shorter filters and DIRECT use the register-blocked
-    // direct form (VALU-bound at 4 L flop / sample).
+    // FAST on complex data with L in [kFirFftMinTaps, 513] (fft_P() <= 512) runs
+    // the overlap-save FFT kernel (HBM-bound); shorter and longer filters and
+    // DIRECT use the register-blocked direct form (VALU-bound at 4 L flop / sample).
     static constexpr int kFirFftMinTaps = 48;
     int fft_P() const { return ((int)h.size() - 1 + 63) / 64 * 64; }
     bool use_fft() const
     {
         const int L = (int)h.size();
         return mode == LDSP_MODE_FAST && cplx && L >= kFirFftMinTaps && fft_P() <= 512;
+    }
+    // the kernel a call of n samples runs (fir_dispatch, ldsp_debug_fir_dispatch)
+    enum Kernel { kDirect = 0, kFft = 1, kExact = 2 };
+    Kernel kernel_for(size_t n) const
+    {
+        if (mode == LDSP_MODE_EXACT) return kExact;
+        return use_fft() && n > 0 ? kFft : kDirect;
     }
     void prepare_fft()
     {
@@ -428,6 +435,19 @@ struct ResampObj {
         if (n == 0) return 0;
         const long long num = (long long)(n - 1) * (1LL << 24) + 0xffffffLL - (long long)phase;
         return num < 0 ? 0 : (size_t)(num / step) + 1;
+    }
+    // the plan of the next call of n samples (ldsp_resamp_execute, ldsp_debug_resamp_dispatch)
+    k::ResampPlan plan(size_t n) const
+    {
+        k::ResampPlan p;
+        p.P0 = phase;
+        p.step = step;
+        p.bits_index = bits_index;
+        p.sub_len = (int)sub_len;
+        p.npfb = (int)npfb;
+        p.K = num_outputs(n);
+        k::resamp_plan(p, cplx, real_taps);
+        return p;
     }
     void ensure_device()
     {
@@ -788,6 +808,17 @@ struct IirObj {
         static const int onex = LDSP_KNOB("LDSP_IIR_ONEXCD", -1);
         p.one_xcd = onex >= 0 ? onex : (units <= 16L * mf.J ? 1 : 0);
         p.variant = LDSP_KNOB("LDSP_IIR_VARIANT", 0);
+        return p;
+    }
+    // Speculative exact chunks (kSpec): warm-up, chunk length and count; the
+    // caller adds the scratch.
+    k::SpecPlan spec_plan(size_t n) const
+    {
+        k::SpecPlan p;
+        p.W = spec_W;
+        p.C = std::max(128, spec_W / 32);   // W + C steps per lane, <= 1/32 redundancy growth
+        p.nchunks = (long)((n + p.C - 1) / p.C);
+        p.scratch = nullptr;
         return p;
     }
     k::IirScanPlan scan_plan(size_t n)
@@ -1433,9 +1464,10 @@ static void fir_dispatch(ldsp_firfilt_s* q, const void* dx, size_t n, void* dy, 
     void* hin = q->hist[q->cur].p;
     void* hout = q->hist[1 - q->cur].p;
     if (L <= 1 && n == 0) return;
-    if (q->mode == LDSP_MODE_EXACT)
+    const FirObj::Kernel kern = q->kernel_for(n);
+    if (kern == FirObj::kExact)
         k::fir_exact(q->cplx, dx, hin, hout, n, q->taps_rev.as<float>(), L, q->scale, dy, s);
-    else if (q->use_fft() && n > 0) {
+    else if (kern == FirObj::kFft) {
         if (!q->fft_ready || q->fft_scale != q->scale) {
             LDSP_HIP(hipStreamSynchronize(s));   // tables may be in use by queued work
             q->prepare_fft();
@@ -1580,25 +1612,7 @@ int ldsp_resamp_execute(ldsp_resamp_t q, const void* x, size_t n, void* y, size_
         const void* dx = q->stg.dev_in(e, x, n * q->esz());
         void* dy = q->stg.dev_out(e, y, K * q->esz());
         if (n > 0) {
-            k::ResampPlan p;
-            p.P0 = q->phase;
-            p.step = q->step;
-            p.bits_index = q->bits_index;
-            p.sub_len = (int)q->sub_len;
-            p.npfb = (int)q->npfb;
-            p.K = K;
-            int KB = 64;
-            auto span_for = [&](int kb) {
-                return (int)(((uint64_t)(kb - 1) * q->step >> 24) + 3 + q->sub_len);
-            };
-            while (KB > 1 && (size_t)span_for(KB) * q->esz() > 48 * 1024) KB >>= 1;
-            p.KB = KB;
-            p.span_max = span_for(KB);
-            const int tkb = k::resamp_tile_outputs(q->step, (int)q->sub_len, (int)q->npfb, q->cplx, q->real_taps);
-            if (tkb > 0) {
-                p.KB = tkb;
-                p.tile = 1;
-            }
+            const k::ResampPlan p = q->plan(n);
             k::resamp(q->cplx, q->real_taps, dx, q->hist[q->cur].p, q->hist[1 - q->cur].p, n, q->dsub.as<float>(), p, dy,
                       e.stream);
             if (q->sub_len > 1) q->cur = 1 - q->cur;
@@ -1899,6 +1913,40 @@ int ldsp_debug_iir_modal_info(ldsp_iirfilt_t q, int* ok, int* modes, int* lookba
         if (err) *err = q->mf.err;
     });
 }
+int ldsp_debug_iir_dispatch(ldsp_iirfilt_t q, size_t n, int* path, int* sect_tile, int* size_class, int* spec_W,
+                            int* spec_staged)
+{
+    return guard([&] {
+        NONNULL(q);
+        const IirObj::Path p = q->path_for(n);
+        const k::IirSeqKernel kq = k::iir_seq_kernel(q->desc());
+        if (path) *path = (int)p;
+        if (sect_tile) *sect_tile = p == IirObj::kSeq ? kq.sect_tile : 0;
+        if (size_class) *size_class = kq.size_class;
+        if (spec_W) *spec_W = q->spec_W;
+        if (spec_staged) *spec_staged = p == IirObj::kSpec && k::iir_spec_staged(q->cplx, q->spec_plan(n)) ? 1 : 0;
+    });
+}
+int ldsp_debug_fir_dispatch(ldsp_firfilt_t q, size_t n, int* kernel, int* points, int* overlap)
+{
+    return guard([&] {
+        NONNULL(q);
+        const FirObj::Kernel kern = q->kernel_for(n);
+        if (kernel) *kernel = (int)kern;
+        if (points) *points = kern == FirObj::kFft ? k::fir_fft_points(q->fft_P()) : 0;
+        if (overlap) *overlap = kern == FirObj::kFft ? q->fft_P() : 0;
+    });
+}
+int ldsp_debug_resamp_dispatch(ldsp_resamp_t q, size_t n, int* kernel, int* outputs_per_group)
+{
+    return guard([&] {
+        NONNULL(q);
+        const k::ResampPlan p = q->plan(n);
+        const k::ResampKernel kern = k::resamp_kernel(p, q->cplx, q->real_taps);
+        if (kernel) *kernel = (int)kern;
+        if (outputs_per_group) *outputs_per_group = kern == k::kResampDirect ? k::kResampDirectOutputs : p.KB;
+    });
+}
 int ldsp_iirfilt_get_sos(ldsp_iirfilt_t q, float* B, float* A)
 {
     return guard([&] {
@@ -1968,10 +2016,7 @@ static int iirfilt_execute(ldsp_iirfilt_t q, const void* x, size_t n, void* y, i
             switch (path) {
             case kSpec: {   // speculative exact chunks (same bits as sequential)
                 q->state_to(IirObj::kSt32, e.stream);
-                k::SpecPlan p;
-                p.W = q->spec_W;
-                p.C = std::max(128, q->spec_W / 32);   // W + C steps per lane, <= 1/32 redundancy growth
-                p.nchunks = (long)((n + p.C - 1) / p.C);
+                k::SpecPlan p = q->spec_plan(n);
                 const size_t need = k::spec_scratch_bytes(p.nchunks, q->ncomp(), q->fsz());
                 p.scratch = q->sc1.ensure(need, q->device);
                 k::iir_spec(q->cplx, d, dx, n, q->st32.as<float>(), p, dy, e.stream);
@@ -3150,8 +3195,7 @@ int ldsp_iirfilt_execute_many(ldsp_iirfilt_t* q, const void* const* x, size_t n,
     return run_many(q, C, stream, [&](int c) {
         const IirObj::Path p = q[c]->path_for(n);
         // exact SOS cascades: k_iir_sect, one workgroup per (object, component)
-        const bool sect = p == IirObj::kSeq && q[c]->sos && q[c]->D > 0 && q[c]->nsos >= 1 &&
-                          q[c]->nsos <= (unsigned)k::kIirSectMaxSos;
+        const bool sect = p == IirObj::kSeq && k::iir_seq_kernel(q[c]->desc()).sect_tile != 0;
         return p == IirObj::kSpec || p == IirObj::kModal || sect;
     }, [&](int c) {
         return ldsp_iirfilt_execute(q[c], x[c], n, y[c], LDSP_MEM_DEVICE, stream);

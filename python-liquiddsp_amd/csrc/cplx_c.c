@@ -210,3 +210,21 @@ void ldsp_bessel_azpkf(unsigned int _n, float *pa_out)
     const float w3dB = sqrtf((2 * _n - 1) * logf(2.0f));
     for (i = 0; i < _n; i++) _pa[i] = (float complex)z[i] / w3dB;
 }
+
+/* liquid iirdes_dzpk_lp2bp: every low-pass root z becomes the two band-pass
+ * roots 0.5 (c0 t0 +- sqrt(c0^2 t0^2 - 4 z)), t0 = 1 + z, c0 = cos(2 pi f0), in C's
+ * float complex arithmetic and with C's csqrtf: std::sqrt(std::complex<float>)
+ * of a HIP translation unit is another algorithm, 1 ulp off for some roots
+ * (the SOS of cheby2 bandpass order 6 and 7, among others).
+ * in: n complex roots, out: 2 n (both interleaved re, im). */
+void ldsp_dzpk_lp2bp(const float *in, unsigned int n, float c0, float *out)
+{
+    const float complex *z = (const float complex *)in;
+    float complex *zt = (float complex *)out;
+    unsigned int i;
+    for (i = 0; i < n; i++) {
+        const float complex t0 = 1 + z[i];
+        zt[2 * i + 0] = 0.5f * (c0 * t0 + csqrtf(c0 * c0 * t0 * t0 - 4 * z[i]));
+        zt[2 * i + 1] = 0.5f * (c0 * t0 - csqrtf(c0 * c0 * t0 * t0 - 4 * z[i]));
+    }
+}

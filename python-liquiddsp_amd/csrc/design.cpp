@@ -32,6 +32,7 @@ extern "C" void ldsp_cdivf(float ar, float ai, float br, float bi, float* out);
 extern "C" void ldsp_cdivd(double ar, double ai, double br, double bi, double* out);
 extern "C" void ldsp_ellip_azpkf(unsigned int n, float ep, float es, float* za, float* pa);
 extern "C" void ldsp_bessel_azpkf(unsigned int n, float* pa);
+extern "C" void ldsp_dzpk_lp2bp(const float* in, unsigned int n, float c0, float* out);
 static inline cf cdiv(cf x, cf y)
 {
     float r[2];
@@ -260,14 +261,10 @@ void bilinear(const std::vector<cf>& za, const std::vector<cf>& pa, cf ka, float
 void lp2bp(std::vector<cf>& zd, std::vector<cf>& pd, float f0)
 {
     const float c0 = cosf((float)(2 * kPi * f0));
-    auto xf = [&](const std::vector<cf>& in) {
+    auto xf = [&](const std::vector<cf>& in) {       // C's complex arithmetic and csqrtf (cplx_c.c)
         std::vector<cf> out(2 * in.size());
-        for (size_t i = 0; i < in.size(); i++) {
-            const cf t0 = 1.0f + in[i];                     // C: 1 + z (real + complex)
-            const cf d = std::sqrt(c0 * c0 * t0 * t0 - 4.0f * in[i]);
-            out[2 * i + 0] = 0.5f * (c0 * t0 + d);
-            out[2 * i + 1] = 0.5f * (c0 * t0 - d);
-        }
+        ldsp_dzpk_lp2bp(reinterpret_cast<const float*>(in.data()), (unsigned int)in.size(), c0,
+                        reinterpret_cast<float*>(out.data()));
         return out;
     };
     zd = xf(zd);

@@ -40,6 +40,8 @@ __device__ __forceinline__ float2 vfma(float h, float2 v, float2 a)
 {
     return make_float2(fmaf(h, v.x, a.x), fmaf(h, v.y, a.y));
 }
+__device__ __forceinline__ float vadd(float a, float b) { return a + b; }
+__device__ __forceinline__ float2 vadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float vscale(float a, float s) { return a * s; }
 __device__ __forceinline__ float2 vscale(float2 a, float s) { return make_float2(a.x * s, a.y * s); }
 // exact accumulate: r = r + h*x (no contraction: library built with -ffp-contract=off)
@@ -100,9 +102,14 @@ __global__ void __launch_bounds__(kThreads) k_fir_fast(const T* __restrict__ x, 
     }
     __syncthreads();
 
-    T acc[kR], A[kR], B[kR];
+    // Two accumulators per output, the 16-tap blocks alternating between them:
+    // each chain of dependent float32 additions is half as long and carries half
+    // the sum, which halves the accumulated rounding error of a long filter (one
+    // chain was, at ~450 taps and more, sometimes further from the float64
+    // convolution than the sequential float32 dot product it replaces).
+    T acc[kR], acc1[kR], A[kR], B[kR];
 #pragma unroll
-    for (int r = 0; r < kR; r++) acc[r] = z;
+    for (int r = 0; r < kR; r++) acc[r] = acc1[r] = z;
     const int base = tid * kR + halo;
 #pragma unroll
     for (int j = 0; j < kR - 1; j++) B[j] = lds[fslot(base + 1 + j)];
@@ -112,14 +119,18 @@ __global__ void __launch_bounds__(kThreads) k_fir_fast(const T* __restrict__ x, 
     int kb = 0;
     for (; kb + 2 <= nfull; kb += 2) {
         fir_kblock<T, false>(acc, A, B, lds, base - kb * kR, h + kb * kR, 0);
-        fir_kblock<T, false>(acc, B, A, lds, base - (kb + 1) * kR, h + (kb + 1) * kR, 0);
+        fir_kblock<T, false>(acc1, B, A, lds, base - (kb + 1) * kR, h + (kb + 1) * kR, 0);
     }
     if (kb < nfull) {
         fir_kblock<T, false>(acc, A, B, lds, base - kb * kR, h + kb * kR, 0);
         kb++;
-        if (rem) fir_kblock<T, true>(acc, B, A, lds, base - kb * kR, h + kb * kR, rem);
+        if (rem) fir_kblock<T, true>(acc1, B, A, lds, base - kb * kR, h + kb * kR, rem);
     } else if (rem) {
         fir_kblock<T, true>(acc, A, B, lds, base - kb * kR, h + kb * kR, rem);
+    }
+    if (L > kR) {        // (up to 16 taps: one block, the second accumulator was never used)
+#pragma unroll
+        for (int r = 0; r < kR; r++) acc[r] = vadd(acc[r], acc1[r]);
     }
 
     __syncthreads();
@@ -493,12 +504,42 @@ int resamp_tile_outputs(uint32_t step, int sub_len, int npfb, bool cplx, bool re
     return bytes(kb) <= 64 * 1024 ? kb : 0;
 }
 
+static size_t resamp_tap_bytes(const ResampPlan& p, bool cplx, bool real_taps)
+{
+    return (size_t)p.npfb * p.sub_len * ((cplx && !real_taps) ? 8 : 4);
+}
+
+void resamp_plan(ResampPlan& p, bool cplx, bool real_taps)
+{
+    // the staged kernel's outputs per workgroup: 64, halved until the span fits 48 KiB
+    const size_t elem = cplx ? 8 : 4;
+    auto span_for = [&](int kb) { return (int)(((uint64_t)(kb - 1) * p.step >> 24) + 3 + p.sub_len); };
+    int KB = 64;
+    while (KB > 1 && (size_t)span_for(KB) * elem > 48 * 1024) KB >>= 1;
+    p.KB = KB;
+    p.span_max = span_for(KB);
+    p.tile = 0;
+    const int tkb = resamp_tile_outputs(p.step, p.sub_len, p.npfb, cplx, real_taps);
+    if (tkb > 0) {
+        p.KB = tkb;
+        p.tile = 1;
+    }
+}
+
+ResampKernel resamp_kernel(const ResampPlan& p, bool cplx, bool real_taps)
+{
+    if (p.KB > 0 && p.tile && p.K > 0) return kResampTile;
+    if (resamp_tap_bytes(p, cplx, real_taps) <= 64 * 1024 && p.K > 0) return kResampDirect;
+    return kResampStaged;       // very large branch tables, and calls without outputs (the history only)
+}
+
 void resamp(bool cplx, bool real_taps, const void* x, const void* hist, void* hist_out, size_t n, const float* sub,
             const ResampPlan& p, void* y, hipStream_t s)
 {
     const size_t elem = cplx ? 8 : 4;
-    const size_t tap_lds = (size_t)p.npfb * p.sub_len * ((cplx && !real_taps) ? 8 : 4);
-    if (p.KB > 0 && p.tile && p.K > 0) {
+    const size_t tap_lds = resamp_tap_bytes(p, cplx, real_taps);
+    const ResampKernel kern = resamp_kernel(p, cplx, real_taps);
+    if (kern == kResampTile) {
         const int tap_bytes = (int)((tap_lds + 15) / 16 * 16);
         const size_t lds = (size_t)tap_bytes + (((uint64_t)(p.KB - 1) * p.step >> 24) + p.sub_len + 4) * elem;
         const unsigned g = (unsigned)((p.K + p.KB - 1) / p.KB);
@@ -522,8 +563,8 @@ void resamp(bool cplx, bool real_taps, const void* x, const void* hist, void* hi
         LDSP_HIP(hipGetLastError());
         return;
     }
-    if (tap_lds <= 64 * 1024 && p.K > 0) {
-        const unsigned g = (unsigned)((p.K + 255) / 256);
+    if (kern == kResampDirect) {
+        const unsigned g = (unsigned)((p.K + kResampDirectOutputs - 1) / kResampDirectOutputs);
         LDSP_PROF(s, "k_resamp");
         if (cplx && real_taps) {
             LDSP_HIP(hipFuncSetAttribute((const void*)k_resamp_direct<true, true>,

@@ -983,17 +983,24 @@ void dispatch_blk(const IirDesc& d, const float* cb, const float* ca, const void
 
 } // namespace
 
+IirSeqKernel iir_seq_kernel(const IirDesc& d)
+{
+    const bool sect = d.sos && d.nsos >= 1 && d.nsos <= kIirSectMaxSos;
+    return IirSeqKernel{sect ? iir_sect_tile(d.nsos) : 0, iir_size_class(d)};
+}
+
 void iir_seq(bool cplx, const IirDesc& d, const void* x, size_t n, float* state, void* y, hipStream_t s)
 {
     if (n == 0) return;
     LDSP_REQUIRE(d.sos ? d.nsos <= kMaxSos : d.nv <= kMaxTf, "iir: filter order too high for the GPU kernels");
-    if (d.sos && d.nsos >= 1 && d.nsos <= kIirSectMaxSos) {     // a wave per section (k_iir_sect.hip)
+    const IirSeqKernel kq = iir_seq_kernel(d);
+    if (kq.sect_tile) {                                          // a wave per section (k_iir_sect.hip)
         iir_sect(cplx, d, x, n, state, y, s);
         return;
     }
     {
         LDSP_PROF(s, "k_iir_seq");
-        const int z = iir_size_class(d);
+        const int z = kq.size_class;
         auto launch = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, s, d, (const float*)x, (long)n, cplx ? 2 : 1, state, (float*)y);
         };
@@ -1014,6 +1021,14 @@ size_t spec_scratch_bytes(long nchunks, int ncomp, int fs)
     return spec_flags_offset(nchunks, ncomp, fs) + (size_t)((nchunks + 63) / 64 + 64) * 8;
 }
 
+// a workgroup's window: 64 / ncomp chunks of C samples + W, ncomp floats each
+static size_t spec_stage_bytes(int ncomp, const SpecPlan& p)
+{
+    return (size_t)4 * (64 * (size_t)p.C + (size_t)ncomp * p.W);
+}
+
+bool iir_spec_staged(bool cplx, const SpecPlan& p) { return spec_stage_bytes(cplx ? 2 : 1, p) <= 64 * 1024; }
+
 void iir_spec(bool cplx, const IirDesc& d, const void* x, size_t n, float* state, const SpecPlan& p, void* y,
               hipStream_t s)
 {
@@ -1022,9 +1037,8 @@ void iir_spec(bool cplx, const IirDesc& d, const void* x, size_t n, float* state
     const long work = p.nchunks * ncomp;
     const int z = iir_size_class(d);
     {
-        // a workgroup's window: 64 / ncomp chunks of C samples + W, ncomp floats each
-        const size_t stage = (size_t)4 * (64 * (size_t)p.C + (size_t)ncomp * p.W);
-        const bool st = stage <= 64 * 1024;
+        const size_t stage = spec_stage_bytes(ncomp, p);
+        const bool st = iir_spec_staged(cplx, p);
         const IirSpecChunksArgs a{d, (const float*)x, (long)n, ncomp, (const float*)state, p.C, p.W, p.nchunks,
                                   (float*)p.scratch, (float*)y};
         const dim3 g((unsigned)((work + 63) / 64)), b(64);
@@ -1078,9 +1092,13 @@ void iir_scan(bool cplx, const IirDesc& d, const void* x, size_t n, double* stat
     case 6: launch_carry<6>(ncomp, p, state64, s); break;
     case 7: launch_carry<7>(ncomp, p, state64, s); break;
     case 8: launch_carry<8>(ncomp, p, state64, s); break;
+    case 9: launch_carry<9>(ncomp, p, state64, s); break;
     case 10: launch_carry<10>(ncomp, p, state64, s); break;
+    case 11: launch_carry<11>(ncomp, p, state64, s); break;
     case 12: launch_carry<12>(ncomp, p, state64, s); break;
+    case 13: launch_carry<13>(ncomp, p, state64, s); break;
     case 14: launch_carry<14>(ncomp, p, state64, s); break;
+    case 15: launch_carry<15>(ncomp, p, state64, s); break;
     case 16: launch_carry<16>(ncomp, p, state64, s); break;
     default:
         throw Error(LDSP_EUNSUP, "iir: unsupported state dimension for the scan kernels");

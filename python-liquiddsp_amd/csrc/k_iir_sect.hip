@@ -387,6 +387,10 @@ unsigned long long* g_sect_trace = nullptr;
 
 } // namespace
 
+constexpr size_t kSectLdsMax = 160 * 1024;
+
+int iir_sect_tile(int nsos) { return sect_lds<1024>(nsos) <= kSectLdsMax ? 1024 : 512; }
+
 int iir_sect_trace(void* dev_buf)
 {
     g_sect_trace = (unsigned long long*)dev_buf;
@@ -408,8 +412,8 @@ void iir_sect(bool cplx, const IirDesc& d, const void* x, size_t n, float* state
     a.state = state;
     a.y = (float*)y;
     a.trace = g_sect_trace;
-    constexpr size_t kLdsMax = 160 * 1024;
-    const bool big = sect_lds<1024>(d.nsos) <= kLdsMax;
+    constexpr size_t kLdsMax = kSectLdsMax;
+    const bool big = iir_sect_tile(d.nsos) == 1024;
     const size_t lds = big ? sect_lds<1024>(d.nsos) : sect_lds<512>(d.nsos);
     auto one = big ? k_iir_sect1024 : k_iir_sect512;
     auto many = big ? k_iir_sect1024_many : k_iir_sect512_many;

@@ -55,6 +55,15 @@ struct ResampPlan {
 };
 // Outputs per workgroup of the tile kernel (0: its LDS would not fit; use the others).
 int resamp_tile_outputs(uint32_t step, int sub_len, int npfb, bool cplx, bool real_taps);
+// The kernel of a call, decided on the host from the plan alone: the tile kernel
+// when its LDS fits; else k_resamp_direct (one output per thread, kResampDirectOutputs
+// per workgroup) while the branch table fits 64 KiB of LDS; else k_resamp, which stages
+// each workgroup's span and also serves the calls without outputs (history only).
+enum ResampKernel { kResampTile = 0, kResampDirect = 1, kResampStaged = 2 };
+constexpr int kResampDirectOutputs = 256;
+// Fills KB, span_max and tile from step, sub_len and npfb (host logic only).
+void resamp_plan(ResampPlan& p, bool cplx, bool real_taps);
+ResampKernel resamp_kernel(const ResampPlan& p, bool cplx, bool real_taps);
 // sub: [npfb][sub_len] branch taps reversed (cccf: complex64 with imag 0; rrrf, crcf: float)
 void resamp(bool cplx, bool real_taps, const void* x, const void* hist, void* hist_out, size_t n, const float* sub,
             const ResampPlan& p, void* y, hipStream_t s);
@@ -84,6 +93,14 @@ constexpr int kIirSectMaxSos = 8;
 // component) (k_iir_sect.hip); mergeable in many-calls.  iir_seq uses it for SOS
 // cascades of <= kIirSectMaxSos sections.
 void iir_sect(bool cplx, const IirDesc& d, const void* x, size_t n, float* state, void* y, hipStream_t s);
+int iir_sect_tile(int nsos);           // its tile: 1024 samples while the rings fit the CU's LDS, else 512
+// What iir_seq launches for d (host logic only): k_iir_sect with tiles of
+// sect_tile samples, or -- sect_tile == 0 -- k_iir_seq<size_class>.  size_class
+// (2, 4 or 17 sections / coefficients) also selects the iir_spec kernels.
+struct IirSeqKernel {
+    int sect_tile, size_class;
+};
+IirSeqKernel iir_seq_kernel(const IirDesc& d);
 int iir_sect_trace(void* dev_buf);     // diagnostics: ldsp_debug_iir_sect_trace
 // Float64 chunked linear scan.  state64: double[2][D] (the DF-II delay line in
 // the layout used by the scan); Apow: double[D*D] matrices: [0] = A^C,
@@ -193,6 +210,8 @@ struct SpecPlan {
 // scratch for iir_spec: chunk states + verifier flag words
 size_t spec_flags_offset(long nchunks, int ncomp, int fs);
 size_t spec_scratch_bytes(long nchunks, int ncomp, int fs);
+// true: k_iir_spec_chunks stages a workgroup's input window in LDS (it fits 64 KiB)
+bool iir_spec_staged(bool cplx, const SpecPlan& p);
 void iir_spec(bool cplx, const IirDesc& d, const void* x, size_t n, float* state, const SpecPlan& p, void* y,
               hipStream_t s);
 

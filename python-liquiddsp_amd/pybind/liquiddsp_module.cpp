@@ -924,6 +924,40 @@ struct RealIIRFilter : ProtoIIR {
         : ProtoIIR(ft, bt, o, fc, f0, ap, as, false) {}
 };
 
+const char* kIirDispatchDoc =
+    "test hook (host logic only): (path, sect_tile, size_class, spec_W, spec_staged) of a call of n samples; path is "
+    "'spec', 'seq', 'modal', 'blk' or 'scan' (ldsp_debug_iir_dispatch)";
+template <typename C>
+py::tuple iir_dispatch(C& c, size_t n)
+{
+    static const char* const names[] = {"spec", "seq", "modal", "blk", "scan"};
+    int path = 0, tile = 0, z = 0, w = 0, st = 0;
+    check(ldsp_debug_iir_dispatch(c.q, n, &path, &tile, &z, &w, &st));
+    return py::make_tuple(names[path], tile, z, w, st != 0);
+}
+template <typename C>
+py::tuple fir_dispatch(C& c, size_t n)
+{
+    static const char* const names[] = {"direct", "fft", "exact"};
+    int kern = 0, points = 0, overlap = 0;
+    check(ldsp_debug_fir_dispatch(c.q, n, &kern, &points, &overlap));
+    return py::make_tuple(names[kern], points, overlap);
+}
+template <typename C>
+py::tuple resamp_dispatch(C& c, size_t n)
+{
+    static const char* const names[] = {"tile", "direct", "staged"};
+    int kern = 0, kb = 0;
+    check(ldsp_debug_resamp_dispatch(c.q, n, &kern, &kb));
+    return py::make_tuple(names[kern], kb);
+}
+const char* kFirDispatchDoc =
+    "test hook (host logic only): (kernel, N, P) of a call of n samples; kernel is 'direct', 'fft' or 'exact', N the "
+    "FFT window and P its overlap (ldsp_debug_fir_dispatch)";
+const char* kResampDispatchDoc =
+    "test hook (host logic only): (kernel, outputs per workgroup) of the next call of n samples; kernel is 'tile', "
+    "'direct' or 'staged' (ldsp_debug_resamp_dispatch)";
+
 template <typename C, typename P>
 void bind_iir_common(P& c)
 {
@@ -941,7 +975,8 @@ void bind_iir_common(P& c)
             double err = 0;
             check(ldsp_debug_iir_modal_info(c.q, &ok, &m, &j, &err));
             return py::make_tuple(ok != 0, m, j, err);
-        });
+        })
+        .def("_dispatch", &iir_dispatch<C>, py::arg("n"), kIirDispatchDoc);
 }
 
 template <typename C>
@@ -989,7 +1024,8 @@ void bind_proto(py::module_& m, const char* name)
             double err = 0;
             check(ldsp_debug_iir_modal_info(c.q, &ok, &m, &j, &err));
             return py::make_tuple(ok != 0, m, j, err);
-        });
+        })
+        .def("_dispatch", &iir_dispatch<C>, py::arg("n"), kIirDispatchDoc);
 }
 
 const char* kResampDoc = "Arbitrary-rate polyphase resampler (liquid resamp_*), runs on the GPU.";
@@ -1350,6 +1386,7 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def("print", &RealResampler::print)
         .def("reset", &RealResampler::reset)
         .def("__call__", &RealResampler::call)
+        .def("_dispatch", &resamp_dispatch<RealResampler>, py::arg("n"), kResampDispatchDoc)
         .def_property("rate", &RealResampler::get_rate, &RealResampler::set_rate);
     py::class_<ComplexResampler>(m, "ComplexResampler", kResampDoc)
         .def(py::init<float, int, float, float, int>(), py::arg("rate"), py::arg("len") = 20, py::arg("Fc"),
@@ -1357,6 +1394,7 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def("print", &ComplexResampler::print)
         .def("reset", &ComplexResampler::reset)
         .def("__call__", &ComplexResampler::call)
+        .def("_dispatch", &resamp_dispatch<ComplexResampler>, py::arg("n"), kResampDispatchDoc)
         .def_property("rate", &ComplexResampler::get_rate, &ComplexResampler::set_rate);
 
     // ---- AGC (wrapper.cpp:228-242)
@@ -1401,6 +1439,7 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def("reset", &RealFIRFilter::reset)
         .def_property("exact", &RealFIRFilter::get_exact, &RealFIRFilter::set_exact)
         .def_property("mode", &RealFIRFilter::get_mode, &RealFIRFilter::set_mode)
+        .def("_dispatch", &fir_dispatch<RealFIRFilter>, py::arg("n"), kFirDispatchDoc)
         .def_property_readonly("taps", &RealFIRFilter::taps);
     py::class_<ComplexFIRFilter>(m, "ComplexFIRFilter")
         .def(py::init<py::handle>(), py::arg("h"))
@@ -1409,6 +1448,7 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def("reset", &ComplexFIRFilter::reset)
         .def_property("exact", &ComplexFIRFilter::get_exact, &ComplexFIRFilter::set_exact)
         .def_property("mode", &ComplexFIRFilter::get_mode, &ComplexFIRFilter::set_mode)
+        .def("_dispatch", &fir_dispatch<ComplexFIRFilter>, py::arg("n"), kFirDispatchDoc)
         .def_property_readonly("taps", &ComplexFIRFilter::taps);
     py::class_<RealDCBlocker>(m, "RealDCBlocker")
         .def(py::init<int, float>(), py::arg("slen") = 25, py::arg("As") = 20.0f)

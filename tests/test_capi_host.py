@@ -121,7 +121,11 @@ PROTOS = [("butter", "lowpass", 4, 0.1, 0.0), ("cheby1", "lowpass", 5, 0.2, 0.0)
           ("butter", "bandpass", 3, 0.1, 0.25), ("cheby1", "bandstop", 2, 0.05, 0.2),
           ("ellip", "lowpass", 4, 0.1, 0.0), ("ellip", "lowpass", 5, 0.2, 0.0), ("ellip", "highpass", 6, 0.05, 0.0),
           ("ellip", "bandpass", 3, 0.1, 0.25), ("bessel", "lowpass", 4, 0.1, 0.0), ("bessel", "lowpass", 7, 0.02, 0.0),
-          ("bessel", "highpass", 3, 0.2, 0.0), ("bessel", "bandstop", 2, 0.05, 0.2)]
+          ("bessel", "highpass", 3, 0.2, 0.0), ("bessel", "bandstop", 2, 0.05, 0.2),
+          # band transforms whose complex square root has to be C's csqrtf to the last bit
+          ("cheby2", "bandpass", 5, 0.05, 0.2), ("cheby2", "bandpass", 6, 0.05, 0.2),
+          ("cheby2", "bandpass", 7, 0.05, 0.2), ("cheby2", "bandpass", 8, 0.05, 0.2),
+          ("butter", "bandstop", 6, 0.05, 0.2), ("cheby2", "bandstop", 5, 0.05, 0.2)]
 FT = {"butter": 0, "cheby1": 1, "cheby2": 2, "ellip": 3, "bessel": 4}
 BT = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}
 

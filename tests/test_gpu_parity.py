@@ -13,11 +13,15 @@ import numpy as np
 import pytest
 import scipy.signal as sps
 
+import dispatch_cases as dc
 from conftest import cgauss, maxrel
 
 pytestmark = pytest.mark.gpu
 
-L_TAPS = [1, 2, 15, 16, 17, 51, 127, 255, 513]
+# the chain's sizes, then every overlap P = 64..512 of the overlap-save path, the
+# tap counts either side of its edges (47/48, 129/130, 513/514) and of the window
+# change, and even block counts of the direct form (32, 64)
+L_TAPS = dc.FIR_TAPS
 
 
 @pytest.fixture(scope="module")
@@ -116,15 +120,30 @@ def test_device_math_bitwise(ld, ora, rng):
 @pytest.mark.parametrize("cplx", [True, False])
 @pytest.mark.parametrize("mode", ["fast", "direct"])
 def test_fir_fast_within_1e6(ld, ora, rng, L, cplx, mode):
-    # complex "fast" with 48 <= L <= 1025 is the overlap-save FFT kernel
+    # complex "fast" with 48 <= L <= 513 (overlap P <= 512) is the overlap-save FFT kernel
+    _fir_fast_case(ld, ora, rng, L, cplx, mode, [0, 1, 5, 4096, 4097, 30_000, 70_001])
+
+
+@pytest.mark.parametrize("L", L_TAPS)
+@pytest.mark.parametrize("cplx", [True, False])
+@pytest.mark.parametrize("mode", ["fast", "direct"])
+def test_fir_fast_hop_cuts(ld, ora, rng, L, cplx, mode):
+    """The same bars over calls cut at the overlap-save hop M = N - P of the tap
+    count: calls that end exactly on a window, one sample short and one over,
+    and calls shorter than the overlap P."""
+    _fir_fast_case(ld, ora, rng, L, cplx, mode, dc.fir_hop_cuts(L))
+
+
+def _fir_fast_case(ld, ora, rng, L, cplx, mode, cuts):
     h = ora.firdes_kaiser(L, 0.1, 60.0) if L > 1 else np.float32([0.7])
-    n = 70_001
+    n = cuts[-1]
     x = cgauss(rng, n) if cplx else np.float32(rng.standard_normal(n))
     g = (ld.ComplexFIRFilter if cplx else ld.RealFIRFilter)(h)
     g.mode = mode
+    for s, e in zip(cuts[:-1], cuts[1:]):
+        assert g._dispatch(e - s) == dc.fir_expected(L, cplx, mode)
     o = ora.FIRFilter(h, cplx=cplx)
     # ragged streaming: history carried across calls
-    cuts = [0, 1, 5, 4096, 4097, 30_000, n]
     y = np.concatenate([g(x[s:e]) for s, e in zip(cuts[:-1], cuts[1:])])
     ref = o(x)
     assert y.dtype == ref.dtype and len(y) == n
@@ -132,6 +151,7 @@ def test_fir_fast_within_1e6(ld, ora, rng, L, cplx, mode):
     # to it as the float32 sequential restatement is
     truth = sps.lfilter(h.astype(np.float64), 1.0, x.astype(np.complex128 if cplx else np.float64))
     err_gpu, err_ref = maxrel(y, truth), maxrel(ref, truth)
+    print(f"FIR L={L} cplx={cplx} {mode} n={n}: gpu {err_gpu:.3g} restatement {err_ref:.3g}")
     # float32 accumulation noise grows ~sqrt(L); beyond the north-star 127 taps the
     # two summation orders are both ~1e-6 from the float64 truth
     assert err_gpu <= max(1e-6, 1.3 * err_ref), (err_gpu, err_ref)
@@ -828,20 +848,26 @@ def test_device_tensor_path_matches_numpy(ld, ora, rng):
 
 
 @pytest.mark.parametrize("cplx", [True, False])
-@pytest.mark.parametrize("order", [1, 2, 5, 8, 16])
+@pytest.mark.parametrize("order", dc.SECT_ORDERS)
 def test_iir_exact_pipeline_call_sizes(ld, ora, rng, cplx, order):
     """Exact mode of an SOS cascade (k_iir_sect: a wave per section, one
-    workgroup per component, 512-sample tiles through 4-tile LDS rings) across
-    calls of every awkward size: shorter than a 32-sample group, odd, one tile
-    +- 1, a ring +- 1, several rings; bit-identical to the sequential
-    restatement and its state carried across."""
-    sizes = [1, 2, 3, 13, 14, 15, 31, 32, 33, 511, 512, 513, 2047, 2048, 2049, 4095, 6000, 3, 40_000]
+    workgroup per component, tiles of 1024 samples -- 512 above 6 sections --
+    through 4-tile LDS rings) of 1..8 sections, odd orders with a first-order
+    section, across calls of every awkward size for both tiles: shorter than a
+    32-sample group, odd, one tile +- 1, a ring +- 1, several rings in one call
+    (12 289 = three laps of the 1024-sample ring + 1); bit-identical to the
+    sequential restatement and its state carried across."""
+    sizes = [1, 2, 3, 13, 14, 15, 31, 32, 33, 511, 512, 513, 2047, 2048, 2049, 4095, 6000, 3, 40_000,
+             1023, 1024, 1025, 4096, 4097, 8191, 8193, 12_289]
     n = sum(sizes)
     x = cgauss(rng, n) if cplx else np.float32(rng.standard_normal(n))
     cls = ld.ComplexIIRFilter if cplx else ld.RealIIRFilter
     g = cls(filter_type="cheby2", order=order, Fc=np.float32(0.02))
     g.exact = True
     g._scan_path(1)              # never the speculative chunks: the sequential exact kernel
+    assert np.asarray(g.sos()[0]).shape[0] == dc.sect_sections(order)
+    for k in sizes:
+        assert g._dispatch(k)[:2] == ("seq", dc.sect_tile(order))
     o = ora.IIRFilter(prototype=("cheby2", "lowpass", 1, order, np.float32(0.02), 0.3, 0.7, 60.0), cplx=cplx)
     out, a = [], 0
     for k in sizes:
