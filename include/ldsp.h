@@ -450,6 +450,38 @@ int ldsp_delay_get_delay(ldsp_delay_t q, unsigned int *nd);
 int ldsp_delay_execute(ldsp_delay_t q, const void *x, size_t n, int cplx, void *y, int mem, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Hilbert transform (firhilbf).  Replaces SSBDemod (src/demod.hpp:155-187,
+ * wrapper.cpp:269-272: firhilbf_create(25, 60) + firhilbf_c2r_execute, one
+ * sideband kept) and HilbertTransform (src/utility.hpp:71-108, wrapper.cpp:174-176:
+ * two firhilbf_create(m, As) objects, firhilbf_interp_execute for complex input
+ * and firhilbf_decim_execute for real input).  Over the stream z = history ++
+ * input (zero history after create / reset), with hq the 2m quadrature taps:
+ *   q[n] = sum_j hq[j] s[n - 4m + 1 + 2j]   (float32, sequential, oldest first)
+ *   R2C    float32[n]   -> complex64[n]     y[n] = (z[n - 2m], q[n]), s = z
+ *   C2R    complex64[n] -> float32[n] (x2)  s = im z, d = re z:
+ *                                           y0[n] = d[n - 2m] + q[n] (lower sideband),
+ *                                           y1[n] = d[n - 2m] - q[n] (upper sideband)
+ *   DECIM  float32[2K]  -> complex64[K]     y[k] = the R2C output at n = 2k + 1
+ *   INTERP complex64[K] -> float32[2K]      y[2k] = im z[k - m],
+ *                                           y[2k + 1] = sum_j hq[j] re z[k + 1 - 2m + j]
+ * Bit-exact with the restatement.  op is fixed per object (liquid's four
+ * functions share the object's windows, so the reference keeps one object per
+ * direction).  n counts input samples.  C2R: either of y0 / y1 may be NULL, not
+ * both; the other ops write y0 and y1 must be NULL.  m < 2, an unknown op and an
+ * odd n for DECIM are LDSP_EINVAL (checked before any device work); m > 64 is
+ * LDSP_EUNSUP.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_firhilb_s *ldsp_firhilb_t;
+enum { LDSP_HILB_R2C = 0, LDSP_HILB_C2R = 1, LDSP_HILB_DECIM = 2, LDSP_HILB_INTERP = 3 };
+int ldsp_firhilb_create(unsigned int m, float as, int op, ldsp_firhilb_t *q);
+int ldsp_firhilb_destroy(ldsp_firhilb_t q);
+int ldsp_firhilb_reset(ldsp_firhilb_t q);
+int ldsp_firhilb_get_taps(ldsp_firhilb_t q, float *hq);          /* 2m floats */
+int ldsp_firhilb_execute(ldsp_firhilb_t q, const void *x, size_t n, void *y0, void *y1, int mem, void *stream);
+/* Test hook: input samples per workgroup of op's kernel (calls cut around it cross a tile edge). */
+int ldsp_debug_firhilb_tile(int op, size_t *samples);
+
+/* ------------------------------------------------------------------------
  * Raw IQ conversion.  Replaces bytes_to_iq (src/utility.hpp:61-69,
  * wrapper.cpp:13): interleaved native int16 (I, Q) -> complex64 / 32767.
  * nbytes / 4 samples are converted (a trailing partial sample is ignored).

@@ -1144,6 +1144,26 @@ struct ldsp_delay_s {
     }
 };
 
+// firhilbf (SSBDemod, HilbertTransform): the 2m quadrature taps and, on the
+// device, the last H input samples in the input's layout, ping-ponged.
+struct ldsp_firhilb_s {
+    unsigned int m = 0;
+    int op = 0;
+    std::vector<float> hq;
+    int device = -1, cur = 0;
+    ldsp::DevBuf dhq, hist[2];
+    hipStream_t last = nullptr;
+    ldsp::StreamMark ord;                  // cross-stream call order (ldsp_common.hpp)
+    ldsp::Staging stg, stg1;               // stg1: the second output of a host-memory C2R call
+    size_t in_size() const { return op == LDSP_HILB_C2R || op == LDSP_HILB_INTERP ? 8 : 4; }
+    size_t hist_bytes() const { return (size_t)(op == LDSP_HILB_INTERP ? 2 * m - 1 : 4 * m - 1) * in_size(); }
+    void zero()
+    {
+        for (auto& b : hist) ldsp::zero_now(b.ensure(hist_bytes(), device), 0, hist_bytes());
+        cur = 0;
+    }
+};
+
 using namespace ldsp;
 
 // Run `fn` translating exceptions into status codes
@@ -2990,6 +3010,101 @@ int ldsp_delay_execute(ldsp_delay_t q, const void* x, size_t n, int cplx, void* 
         q->ord.mark(e.stream);
         q->last = e.stream;
         q->stg.finish(e, y, n * es);
+    });
+}
+
+// ---------------------------------------------------------------- firhilbf
+static_assert(LDSP_HILB_R2C == k::kHilbR2C && LDSP_HILB_C2R == k::kHilbC2R && LDSP_HILB_DECIM == k::kHilbDecim &&
+                  LDSP_HILB_INTERP == k::kHilbInterp,
+              "ldsp.h and kernels.hpp number the Hilbert operations alike");
+int ldsp_firhilb_create(unsigned int m, float as, int op, ldsp_firhilb_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(m >= 2, "firhilb: filter semi-length must be at least 2");
+        LDSP_REQUIRE(op == LDSP_HILB_R2C || op == LDSP_HILB_C2R || op == LDSP_HILB_DECIM || op == LDSP_HILB_INTERP,
+                     "firhilb: op must be one of LDSP_HILB_R2C, _C2R, _DECIM, _INTERP");
+        if (m > (unsigned)k::kHilbMaxM)
+            throw Error(LDSP_EUNSUP, "firhilb: semi-length above " + std::to_string(k::kHilbMaxM) + " is not implemented");
+        std::unique_ptr<ldsp_firhilb_s> o(new ldsp_firhilb_s());
+        o->m = m;
+        o->op = op;
+        o->hq = design::firhilb_taps(m, as);
+        *q = o.release();
+    });
+}
+int ldsp_firhilb_destroy(ldsp_firhilb_t q)
+{
+    return guard([&] {
+        if (q && q->last) (void)hipStreamSynchronize(q->last);
+        delete q;
+    });
+}
+int ldsp_firhilb_reset(ldsp_firhilb_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (q->device < 0) return;
+        DeviceGuard g(q->device);
+        if (q->last) LDSP_HIP(hipStreamSynchronize(q->last));
+        q->ord.sync();
+        q->zero();
+    });
+}
+int ldsp_firhilb_get_taps(ldsp_firhilb_t q, float* hq)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(hq);
+        std::copy(q->hq.begin(), q->hq.end(), hq);
+    });
+}
+int ldsp_firhilb_execute(ldsp_firhilb_t q, const void* x, size_t n, void* y0, void* y1, int mem, void* stream)
+{
+    LDSP_RANGE("ldsp_firhilb_execute");
+    return guard([&] {
+        NONNULL(q);
+        const int op = q->op;
+        if (op == LDSP_HILB_C2R) LDSP_REQUIRE(y0 || y1, "firhilb_execute: c2r needs y0 (lower) or y1 (upper)");
+        else LDSP_REQUIRE(!y1, "firhilb_execute: y1 must be NULL unless the object is c2r");
+        LDSP_REQUIRE(op != LDSP_HILB_DECIM || n % 2 == 0, "firhilb_execute: decim takes an even number of samples");
+        LDSP_REQUIRE(n == 0 || (x && (y0 || op == LDSP_HILB_C2R)), "firhilb_execute: NULL buffer");
+        const BufDevice bd(mem, x);
+        if (q->device < 0) {
+            const int dev = current_device();
+            DeviceGuard g(dev);
+            std::vector<float> pad(q->hq);
+            pad.resize(pad.size() + k::kHilbTapPad, 0.0f);
+            upload(q->dhq, pad, dev);
+            q->device = dev;
+            q->zero();
+        }
+        DeviceGuard g(q->device);
+        const Exec e = make_exec(q->device, mem, stream, bd);
+        q->ord.wait(e.stream);
+        // output samples and their size
+        const size_t no = op == LDSP_HILB_DECIM ? n / 2 : (op == LDSP_HILB_INTERP ? 2 * n : n);
+        const size_t os = op == LDSP_HILB_R2C || op == LDSP_HILB_DECIM ? 8 : 4;
+        const void* dx = q->stg.dev_in(e, x, n * q->in_size());
+        void* d0 = y0 ? q->stg.dev_out(e, y0, no * os) : nullptr;
+        void* d1 = y1 ? q->stg1.dev_out(e, y1, no * os) : nullptr;
+        if (n > 0) {
+            k::hilbert(op, dx, q->hist[q->cur].p, q->hist[1 - q->cur].p, n, q->dhq.as<float>(), (int)q->m, d0, d1,
+                       e.stream);
+            q->cur = 1 - q->cur;
+        }
+        q->ord.mark(e.stream);
+        q->last = e.stream;
+        if (y0) q->stg.finish(e, y0, no * os);
+        if (y1) q->stg1.finish(e, y1, no * os);
+    });
+}
+int ldsp_debug_firhilb_tile(int op, size_t* samples)
+{
+    return guard([&] {
+        NONNULL(samples);
+        LDSP_REQUIRE(op >= LDSP_HILB_R2C && op <= LDSP_HILB_INTERP, "firhilb: unknown op");
+        *samples = op == LDSP_HILB_INTERP ? k::kHilbTile / 2 : k::kHilbTile;
     });
 }
 

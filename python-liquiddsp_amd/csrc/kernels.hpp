@@ -314,6 +314,19 @@ void ssb_v1(const void* idx, const void* x, const void* dhist, int m, const floa
             hipStream_t s);
 void ssb_c2r(const void* x, const void* hist, size_t n, const float* hq, int M, int usb, float mod_index, float* y,
              hipStream_t s);
+// k_hilbert.hip: firhilbf for SSBDemod / HilbertTransform.  op as LDSP_HILB_*;
+// x: n input samples (C2R, INTERP complex64; R2C, DECIM float32, n even for
+// DECIM); hist / hist_out: the H input samples before x[0] / before the next
+// call's x[0], in the input's layout (H = 4M - 1; INTERP 2M - 1), distinct
+// buffers; hq: the 2M quadrature taps followed by kHilbTapPad readable floats
+// (the kernel fetches taps one step ahead).  C2R writes the lower sideband to y0
+// and the upper to y1 (either may be null); the other ops write y0.
+enum HilbOp { kHilbR2C = 0, kHilbC2R = 1, kHilbDecim = 2, kHilbInterp = 3 };
+constexpr int kHilbTapPad = 4;
+constexpr int kHilbMaxM = 64;         // semi-length bound (the LDS planes), as AmpModem's Hilbert stage
+constexpr int kHilbTile = 2048;       // input samples per workgroup (INTERP: half as many)
+void hilbert(int op, const void* x, const void* hist, void* hist_out, size_t n, const float* hq, int M, void* y0,
+             void* y1, hipStream_t s);
 struct FmState {          // FMStereo mixer loop state (device-resident)
     uint32_t theta, dtheta;
     float pe, alpha, beta;

@@ -857,6 +857,111 @@ struct Delay {
     }
 };
 
+// ------------------------------------------------------------------ firhilbf (demod.hpp:155-187, utility.hpp:71-108)
+struct Hilb {
+    ldsp_firhilb_t q = nullptr;
+    Hilb(int m, float as, int op)
+    {
+        if (m < 0) throw py::value_error("firhilb: m must be >= 2");
+        check(ldsp_firhilb_create((unsigned)m, as, op, &q));
+    }
+    Hilb(const Hilb&) = delete;
+    ~Hilb()
+    {
+        if (q) ldsp_firhilb_destroy(q);
+    }
+    // One call: n input samples -> nout(n) outputs per returned array; two arrays
+    // (lower, upper) when `both`, else the output goes to y0 (y1 when `second`).
+    py::object run(const py::handle& x, bool cin, bool cout, size_t (*nout)(size_t), bool both = false,
+                   bool second = false)
+    {
+        auto pick = [&](void* a, void* b, void** y0, void** y1) {
+            *y0 = both || !second ? a : nullptr;
+            *y1 = both ? b : (second ? a : nullptr);
+        };
+        void *y0, *y1;
+        if (is_device_tensor(x)) {
+            DevIn d = dev_in(x, cin);
+            py::object o0 = dev_empty(nout(d.n), cout, d.device);
+            py::object o1 = both ? dev_empty(nout(d.n), cout, d.device) : py::none();
+            pick(tptr(o0), both ? tptr(o1) : nullptr, &y0, &y1);
+            check(ldsp_firhilb_execute(q, d.ptr, d.n, y0, y1, LDSP_MEM_DEVICE, d.stream));
+            return both ? py::object(py::make_tuple(o0, o1)) : o0;
+        }
+        py::array a = cin ? py::array(carr::ensure(x)) : py::array(farr::ensure(x));
+        if (!a) throw py::error_already_set();
+        const size_t n = (size_t)a.size();
+        py::array o0 = host_array(nout(n), cout);
+        py::array o1 = both ? host_array(nout(n), cout) : py::array();
+        pick(o0.mutable_data(), both ? o1.mutable_data() : nullptr, &y0, &y1);
+        const void* xp = a.data();
+        int rc;
+        {
+            py::gil_scoped_release rel;
+            rc = ldsp_firhilb_execute(q, xp, n, y0, y1, LDSP_MEM_HOST, nullptr);
+        }
+        check(rc);
+        return both ? py::object(py::make_tuple(o0, o1)) : py::object(o0);
+    }
+    static size_t same(size_t n) { return n; }
+    static size_t half(size_t n) { return n / 2; }
+    static size_t twice(size_t n) { return 2 * n; }
+};
+
+// SSBDemod (demod.hpp:155-187): firhilbf_create(25, 60), c2r, one sideband kept
+struct SSBDemod {
+    bool usb;
+    Hilb h;
+    explicit SSBDemod(const std::string& band) : usb(band == "usb"), h(25, 60.0f, LDSP_HILB_C2R) {}
+    void reset() { check(ldsp_firhilb_reset(h.q)); }
+    py::object call(const py::handle& x) { return h.run(x, true, false, &Hilb::same, false, usb); }
+};
+
+// HilbertTransform (utility.hpp:71-108): one firhilbf per direction, each with
+// its own state.  The reference calls the 2:1 functions once per input sample
+// with &y[n] / &z[n] (overrunning both buffers by one sample, keeping one of two
+// interpolator outputs and feeding the decimator overlapping pairs); this class
+// keeps the contract of the liquid functions it names: complex64[K] ->
+// float32[2K] (interp) and float32[2K] -> complex64[K] (decim).  INTEGRATION.md.
+struct HilbertTransform {
+    int m;
+    float as;
+    std::unique_ptr<Hilb> o[4];
+    HilbertTransform(int m_, float as_) : m(m_), as(as_)
+    {
+        get(LDSP_HILB_INTERP);
+        get(LDSP_HILB_DECIM);
+    }
+    Hilb& get(int op)
+    {
+        if (!o[op]) o[op].reset(new Hilb(m, as, op));
+        return *o[op];
+    }
+    void reset()
+    {
+        for (auto& h : o)
+            if (h) check(ldsp_firhilb_reset(h->q));
+    }
+    py::object interp(const py::handle& x) { return get(LDSP_HILB_INTERP).run(x, true, false, &Hilb::twice); }
+    py::object decim(const py::handle& x) { return get(LDSP_HILB_DECIM).run(x, false, true, &Hilb::half); }
+    py::object r2c(const py::handle& x) { return get(LDSP_HILB_R2C).run(x, false, true, &Hilb::same); }
+    py::object c2r(const py::handle& x) { return get(LDSP_HILB_C2R).run(x, true, false, &Hilb::same, true); }
+    // dispatch on dtype like Delay: complex64 -> interp, float32 -> decim, anything else -> None
+    py::object call(const py::handle& x)
+    {
+        py::object tp = py::getattr(x, "dtype");
+        if (is_device_tensor(x)) {
+            py::object& torch = torch_mod();
+            if (tp.equal(torch.attr("complex64"))) return interp(x);
+            if (tp.equal(torch.attr("float32"))) return decim(x);
+        } else {
+            if (tp.equal(py::dtype("complex64"))) return interp(x);
+            if (tp.equal(py::dtype("float32"))) return decim(x);
+        }
+        return py::none();
+    }
+};
+
 // bytes_to_iq (utility.hpp:61-69): bytes-like -> numpy complex64; a uint8/int16
 // device tensor -> complex64 device tensor
 py::object bytes_to_iq(const py::handle& b)
@@ -1349,6 +1454,25 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def(py::init<int>(), py::arg("nd") = 1)
         .def_property("delay", &Delay::get_delay, &Delay::set_delay)
         .def("__call__", &Delay::call);
+
+    // ---- SSBDemod (wrapper.cpp:269-272), HilbertTransform (wrapper.cpp:174-176)
+    py::class_<SSBDemod>(m, "SSBDemod")
+        .def(py::init<std::string>(), py::arg("band"))
+        .def("reset", &SSBDemod::reset)
+        .def("__call__", &SSBDemod::call);
+    py::class_<HilbertTransform>(m, "HilbertTransform")
+        .def(py::init<int, float>(), py::arg("m") = 5, py::arg("As") = 60.0f)
+        .def("reset", &HilbertTransform::reset)
+        .def("interp", &HilbertTransform::interp, "complex64[K] -> float32[2K] (firhilbf_interp_execute)")
+        .def("decim", &HilbertTransform::decim, "float32[2K] -> complex64[K] (firhilbf_decim_execute)")
+        .def("r2c", &HilbertTransform::r2c, "float32[n] -> complex64[n] (firhilbf_r2c_execute)")
+        .def("c2r", &HilbertTransform::c2r, "complex64[n] -> (lower, upper) float32[n] (firhilbf_c2r_execute)")
+        .def("__call__", &HilbertTransform::call);
+    m.def("_hilbert_tile", [](int op) {
+        size_t t = 0;
+        check(ldsp_debug_firhilb_tile(op, &t));
+        return t;
+    }, "input samples per workgroup of the Hilbert kernel of op (0 r2c, 1 c2r, 2 decim, 3 interp)");
 
     // ---- FreqDem (wrapper.cpp:183-187), BroadcastAM (wrapper.cpp:259-262)
     py::class_<FreqDem>(m, "FreqDem")
