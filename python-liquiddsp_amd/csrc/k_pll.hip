@@ -1413,7 +1413,12 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
 // Per repair (exec-masked): j = ff1(VCC); exec = the lanes above j; dk1, dk2' = lane
 // j's (readlane, which ignores exec); x += dk2' + srel dk1 in those lanes only; VCC =
 // their events (a VOPC writes 0 for inactive lanes, so VCC is already "events after
-// j": no s_and on the chain, and the loop branches on VCCZ).  Lane j itself keeps its
+// j": no s_and on the chain, and the loop branches on VCCZ).  The scalar accumulators
+// Kb, D follow the compare, not the update: a lone wave issues in order, one
+// instruction every ~8 clocks, so two s_add in front of the v_cmp held the compare --
+// and with it the VCCZ branch and the next s_ff1 -- back by ~14 clocks per repair, while
+// behind it they issue during the wait for VCC that the branch has anyway
+// (scripts/ubench/walk_loop.hip V10 against V15 / V17).  Lane j itself keeps its
 // pre-repair offset, so after the loop the repaired lanes are exactly those whose x
 // is still > W (PM), and the interval test reads x_pre - (L' - dk2) <= span (E0.w).
 // No snapshot, no PM bookkeeping, no next-lane-block update inside the loop: the next
@@ -1427,9 +1432,22 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "v_readlane_b32 %[dk2], " E1Y ", %[j]\n\t"                                                             \
     "v_mad_i32_i24 " X ", " SX ", %[dk1], " X "\n\t"                                                       \
     "v_add_u32 " X ", %[dk2], " X "\n\t"                                                                   \
+    "v_cmp_gt_u32_e32 vcc, " X ", " W "\n\t"                                                               \
+    "s_add_u32 %[kb], %[kb], %[dk2]\n\t"                                                                   \
+    "s_add_u32 %[d], %[d], %[dk1]\n\t"
+#ifdef LDSP_TUNING
+// The accumulators in front of the compare, as before (timing A/B: k_pll_walk VAR 160)
+#define WX_REP_PRE(E1X, E1Y, SX, W, X)                                                                     \
+    "s_ff1_i32_b64 %[j], vcc\n\t"                                                                          \
+    "s_lshl_b64 exec, -2, %[j]\n\t"                                                                        \
+    "v_readlane_b32 %[dk1], " E1X ", %[j]\n\t"                                                             \
+    "v_readlane_b32 %[dk2], " E1Y ", %[j]\n\t"                                                             \
+    "v_mad_i32_i24 " X ", " SX ", %[dk1], " X "\n\t"                                                       \
+    "v_add_u32 " X ", %[dk2], " X "\n\t"                                                                   \
     "s_add_u32 %[kb], %[kb], %[dk2]\n\t"                                                                   \
     "s_add_u32 %[d], %[d], %[dk1]\n\t"                                                                     \
     "v_cmp_gt_u32_e32 vcc, " X ", " W "\n\t"
+#endif
 // The lane-block transition: the next lane-block's offsets (v_mul_lo, quarter
 // rate, then v_add3) are the critical path into its VCCZ branch, so the
 // independent work -- this lane-block's repaired mask, store offset and interval
@@ -1460,6 +1478,30 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "s_bcnt1_i32_b64 %[nr], %[pm]\n\t"                                                                     \
     "s_add_u32 %[nrep], %[nrep], %[nr]\n\t" TAIL
 #ifdef LDSP_TUNING
+// The product lane-block around WX_REP_PRE (k_pll_walk VAR 160)
+#define WL_LB_PRE(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, TAIL)                           \
+    "s_cbranch_vccz 2f\n"                                                                                  \
+    "1:\n\t"                                                                                               \
+    WX_REP_PRE(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                              \
+    WX_REP_PRE(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                              \
+    WX_REP_PRE(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                              \
+    WX_REP_PRE(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccnz 1b\n"                                                \
+    "3:\n\t"                                                                                               \
+    "s_mov_b64 exec, -1\n"                                                                                 \
+    "2:\n\t"                                                                                               \
+    "v_mul_lo_u32 %[t2], %[d], " SXN "\n\t"                                                                \
+    "v_cmp_gt_u32_e64 %[pm], " X ", " E0Y "\n\t"                                                           \
+    "v_lshl_add_u32 %[off], " E0Z ", 2, %[s4]\n\t"                                                         \
+    "v_sub_u32 %[t], " X ", " E0W "\n\t"                                                                   \
+    "v_sub_u32_e64 %[t], %[t], " E1W " clamp\n\t"                                                          \
+    "v_add3_u32 " XN ", " N0X ", %[kb], %[t2]\n\t"                                                         \
+    "s_mov_b64 exec, %[pm]\n\t"                                                                            \
+    "global_store_dword %[off], " E1Z ", %[yb]\n\t"                                                        \
+    "v_or_b32 %[acc], %[acc], %[t]\n\t"                                                                    \
+    "s_mov_b64 exec, -1\n\t"                                                                               \
+    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t"                                                            \
+    "s_bcnt1_i32_b64 %[nr], %[pm]\n\t"                                                                     \
+    "s_add_u32 %[nrep], %[nrep], %[nr]\n\t" TAIL
 // Round 4's lane-block order (timing A/B against WL_LB: k_pll_walk VAR 128)
 #define WL_LB_ORIG(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, TAIL)                           \
     "s_cbranch_vccz 2f\n"                                                                                  \
@@ -1649,7 +1691,8 @@ struct WalkLoop {
 
 // Runs blocks c .. nblk - 1 until one fails its interval test (returns with c = that
 // block, not yet barriered) or all are done (c = nblk).  PV: 0 the product, 1 / 2 the
-// tuning build's timing variants (WL_LB_NOREP / WL_LB_NOST).
+// tuning build's timing variants (WL_LB_NOREP / WL_LB_NOST), 4 / 5 earlier orders
+// (WL_LB_ORIG / WL_LB_PRE).
 template <int PV>
 __device__ __forceinline__ void walk_asm_loop(WalkLoop& w, uint32_t nblk, uint32_t ring, float* y, uint32_t lane16,
                                               uint32_t xs = 0)
@@ -1673,6 +1716,8 @@ __device__ __forceinline__ void walk_asm_loop(WalkLoop& w, uint32_t nblk, uint32
         WALK_ASM(WL_LB_NOST);
     } else if constexpr (PV == 4) {
         WALK_ASM(WL_LB_ORIG);
+    } else if constexpr (PV == 5) {
+        WALK_ASM(WL_LB_PRE);
     } else {
         WALK_ASM(WL_LB_HELPER);
     }
@@ -1771,7 +1816,7 @@ __device__ __forceinline__ void k_pll_walk_body(PllIn in, long n, AmpState* st, 
 #ifdef LDSP_TUNING
     unsigned long long cyc_undo = 0, cyc_fb = 0;      // product loop's block redos: undo pass, fallback lane-blocks
 #endif
-    static_assert(VAR == 0 || VAR == 32 || VAR == 64 || VAR == 96 || VAR == 128, "walker variant");
+    static_assert(VAR == 0 || VAR == 32 || VAR == 64 || VAR == 96 || VAR == 128 || VAR == 160, "walker variant");
     if constexpr (F24 && !STATS) {
         // the product path: the block loop in one asm statement (walk_asm_loop)
         if (wave != 0) {
@@ -2182,6 +2227,7 @@ void pll_back(const PllCall& c, hipStream_t s)
                 case 64: WALK_LAUNCH(true, false, 64); break;
                 case 96: WALK_LAUNCH(true, false, 96); break;
                 case 128: WALK_LAUNCH(true, false, 128); break;
+                case 160: WALK_LAUNCH(true, false, 160); break;
                 default: break;
                 }
                 return;

@@ -2,7 +2,9 @@
 // lane-block is an event (W = 0), so each lane-block runs 64 dependent repairs.
 // Reports device cycles (s_memtime) per repair for loop variants.
 //   hipcc --offload-arch=gfx950 -O3 walk_loop.hip -o walk_loop && ./walk_loop
-// V10 is the product loop since round 4 (k_pll.hip WX_REP); V8 the round-3 one.
+// V17 is the product loop (k_pll.hip WX_REP); V10 the one before it (the scalar
+// accumulators in front of the compare), V8 round 3's.  V12-V14 try a one-sided event
+// test (one VALU hop fewer per repair), V15 / V16 price the instructions beside the chain.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -160,6 +162,111 @@ __global__ void __launch_bounds__(64) k_loop(const uint4* E, uint32_t* out, int 
             acc += x;
             x = e.x;
             continue;
+        } else if (V == 12 || V == 13) {  // one-sided event test: the uniform part dk2' goes into a
+            // per-lane threshold wp (wp -= sg dk2', sg = +-1 the lane's crossing direction) beside the
+            // x update instead of after it, and one signed compare follows: four hops, not five.
+            // V13: the threshold by a plain subtract (every lane "up"), to price the second mad.
+            uint32_t j, dk1, dk2, wp = W, sg = 0xffffffffu;
+#define WO_BODY(WPUPD) \
+    "s_ff1_i32_b64 %[j], vcc\n\t" \
+    "s_lshl_b64 exec, -2, %[j]\n\t" \
+    "v_readlane_b32 %[dk1], %[e1x], %[j]\n\t" \
+    "v_readlane_b32 %[dk2], %[e1y], %[j]\n\t" \
+    "v_mad_i32_i24 %[x], %[sx], %[dk1], %[x]\n\t" \
+    WPUPD \
+    "s_add_u32 %[kb], %[kb], %[dk2]\n\t" \
+    "s_add_u32 %[d], %[d], %[dk1]\n\t" \
+    "v_cmp_gt_i32_e32 vcc, %[x], %[wp]\n\t"
+#define WO_MAD "v_mad_i32_i24 %[wp], %[sg], %[dk2], %[wp]\n\t"
+#define WO_SUB "v_sub_u32 %[wp], %[wp], %[dk2]\n\t"
+#define WO_OPS \
+    : [x] "+v"(x), [wp] "+v"(wp), [kb] "+s"(Kb), [d] "+s"(D), [j] "=&s"(j), [dk1] "=&s"(dk1), [dk2] "=&s"(dk2) \
+    : [e1x] "v"(d1), [e1y] "v"(d2), [sx] "v"(sx), [sg] "v"(sg), [b] "s"(b) : "scc", "vcc", "exec"
+            if (V == 12)
+                asm volatile("v_add_u32 %[x], %[b], %[x]\n\tv_cmp_gt_i32_e32 vcc, %[x], %[wp]\n\t"
+                             "s_cbranch_vccz 2f\n1:\n\t" WO_BODY(WO_MAD) "s_cbranch_vccz 2f\n\t" WO_BODY(WO_MAD)
+                             "s_cbranch_vccz 2f\n\t" WO_BODY(WO_MAD) "s_cbranch_vccz 2f\n\t" WO_BODY(WO_MAD)
+                             "s_cbranch_vccnz 1b\n2:\n\ts_mov_b64 exec, -1" WO_OPS);
+            else
+                asm volatile("v_add_u32 %[x], %[b], %[x]\n\tv_cmp_gt_i32_e32 vcc, %[x], %[wp]\n\t"
+                             "s_cbranch_vccz 2f\n1:\n\t" WO_BODY(WO_SUB) "s_cbranch_vccz 2f\n\t" WO_BODY(WO_SUB)
+                             "s_cbranch_vccz 2f\n\t" WO_BODY(WO_SUB) "s_cbranch_vccz 2f\n\t" WO_BODY(WO_SUB)
+                             "s_cbranch_vccnz 1b\n2:\n\ts_mov_b64 exec, -1" WO_OPS);
+            // the repaired lanes' true pre-repair offset, as the product forms it after the loop
+            acc += x + (W - wp);
+            x = e.x;
+            continue;
+        } else if (V == 14) {    // as V13 with the threshold in an SGPR (every lane the same crossing
+            // direction): the uniform part never reaches the VALU, two VALU ops per repair, not three
+            uint32_t j, dk1, dk2, T = 0;
+#define WS_BODY \
+    "s_ff1_i32_b64 %[j], vcc\n\t" \
+    "s_lshl_b64 exec, -2, %[j]\n\t" \
+    "v_readlane_b32 %[dk1], %[e1x], %[j]\n\t" \
+    "v_readlane_b32 %[dk2], %[e1y], %[j]\n\t" \
+    "v_mad_i32_i24 %[x], %[sx], %[dk1], %[x]\n\t" \
+    "s_sub_u32 %[T], %[T], %[dk2]\n\t" \
+    "s_add_u32 %[d], %[d], %[dk1]\n\t" \
+    "v_cmp_lt_i32_e32 vcc, %[T], %[x]\n\t"
+            asm volatile("v_add_u32 %[x], %[b], %[x]\n\tv_cmp_lt_i32_e32 vcc, %[T], %[x]\n\t"
+                         "s_cbranch_vccz 2f\n1:\n\t" WS_BODY "s_cbranch_vccz 2f\n\t" WS_BODY "s_cbranch_vccz 2f\n\t"
+                         WS_BODY "s_cbranch_vccz 2f\n\t" WS_BODY "s_cbranch_vccnz 1b\n2:\n\ts_mov_b64 exec, -1"
+                         : [x] "+v"(x), [T] "+s"(T), [d] "+s"(D), [j] "=&s"(j), [dk1] "=&s"(dk1), [dk2] "=&s"(dk2)
+                         : [e1x] "v"(d1), [e1y] "v"(d2), [sx] "v"(sx), [b] "s"(b) : "scc", "vcc", "exec");
+            Kb -= T;             // (timing only: a lane's true offset needs T as of its own repair)
+            acc += x;
+            x = e.x;
+            continue;
+        } else if (V == 15 || V == 16 || V == 17) {  // what the instructions in the chain's shadow cost: V10
+            // without its two s_add (V15; timing only, Kb and D are not kept), with two more (V16), and
+            // with its two behind the v_cmp instead of in front of it (V17: the product loop)
+            uint32_t j, dk1, dk2, k2 = 0, d2x = 0;
+#define WY_BODY(ACC) \
+    "s_ff1_i32_b64 %[j], vcc\n\t" \
+    "s_lshl_b64 exec, -2, %[j]\n\t" \
+    "v_readlane_b32 %[dk1], %[e1x], %[j]\n\t" \
+    "v_readlane_b32 %[dk2], %[e1y], %[j]\n\t" \
+    "v_mad_i32_i24 %[x], %[sx], %[dk1], %[x]\n\t" \
+    "v_add_u32 %[x], %[dk2], %[x]\n\t" \
+    ACC \
+    "v_cmp_gt_u32_e32 vcc, %[x], %[w]\n\t"
+#define WZ_BODY \
+    "s_ff1_i32_b64 %[j], vcc\n\t" \
+    "s_lshl_b64 exec, -2, %[j]\n\t" \
+    "v_readlane_b32 %[dk1], %[e1x], %[j]\n\t" \
+    "v_readlane_b32 %[dk2], %[e1y], %[j]\n\t" \
+    "v_mad_i32_i24 %[x], %[sx], %[dk1], %[x]\n\t" \
+    "v_add_u32 %[x], %[dk2], %[x]\n\t" \
+    "v_cmp_gt_u32_e32 vcc, %[x], %[w]\n\t" \
+    "s_add_u32 %[kb], %[kb], %[dk2]\n\t" \
+    "s_add_u32 %[d], %[d], %[dk1]\n\t"
+#define WY_ACC4 \
+    "s_add_u32 %[kb], %[kb], %[dk2]\n\t" \
+    "s_add_u32 %[d], %[d], %[dk1]\n\t" \
+    "s_add_u32 %[k2], %[k2], %[dk2]\n\t" \
+    "s_add_u32 %[d2x], %[d2x], %[dk1]\n\t"
+#define WY_OPS \
+    : [x] "+v"(x), [kb] "+s"(Kb), [d] "+s"(D), [k2] "+s"(k2), [d2x] "+s"(d2x), [j] "=&s"(j), [dk1] "=&s"(dk1), \
+      [dk2] "=&s"(dk2) \
+    : [e1x] "v"(d1), [e1y] "v"(d2), [sx] "v"(sx), [w] "v"(W), [b] "s"(b) : "scc", "vcc", "exec"
+            if (V == 15)
+                asm volatile("v_add_u32 %[x], %[b], %[x]\n\tv_cmp_gt_u32_e32 vcc, %[x], %[w]\n\t"
+                             "s_cbranch_vccz 2f\n1:\n\t" WY_BODY("") "s_cbranch_vccz 2f\n\t" WY_BODY("")
+                             "s_cbranch_vccz 2f\n\t" WY_BODY("") "s_cbranch_vccz 2f\n\t" WY_BODY("")
+                             "s_cbranch_vccnz 1b\n2:\n\ts_mov_b64 exec, -1" WY_OPS);
+            else if (V == 17)
+                asm volatile("v_add_u32 %[x], %[b], %[x]\n\tv_cmp_gt_u32_e32 vcc, %[x], %[w]\n\t"
+                             "s_cbranch_vccz 2f\n1:\n\t" WZ_BODY "s_cbranch_vccz 2f\n\t" WZ_BODY
+                             "s_cbranch_vccz 2f\n\t" WZ_BODY "s_cbranch_vccz 2f\n\t" WZ_BODY
+                             "s_cbranch_vccnz 1b\n2:\n\ts_mov_b64 exec, -1" WY_OPS);
+            else
+                asm volatile("v_add_u32 %[x], %[b], %[x]\n\tv_cmp_gt_u32_e32 vcc, %[x], %[w]\n\t"
+                             "s_cbranch_vccz 2f\n1:\n\t" WY_BODY(WY_ACC4) "s_cbranch_vccz 2f\n\t" WY_BODY(WY_ACC4)
+                             "s_cbranch_vccz 2f\n\t" WY_BODY(WY_ACC4) "s_cbranch_vccz 2f\n\t" WY_BODY(WY_ACC4)
+                             "s_cbranch_vccnz 1b\n2:\n\ts_mov_b64 exec, -1" WY_OPS);
+            acc += x + k2 + d2x;
+            x = e.x;
+            continue;
         } else if (V == 3) {     // pure SALU loop over the mask (no ballot per step)
             do {
                 const int j = __builtin_ctzll(mask);
@@ -212,6 +319,26 @@ int main()
     int same = 1;
     for (int i = 0; i < 64; i++) same &= o10[i] == o11[i];
     printf("V11 results %s V10's\n", same ? "equal" : "DIFFER FROM");
+    // V10 against the one-sided forms in turn: the spread over the rounds is the
+    // repeatability that a difference has to exceed
+    for (int r = 0; r < 5; r++) {
+        run(k_loop<10>, "V10 exec-masked, VCC branch, unrolled x4");
+        run(k_loop<12>, "V12 one-sided test, two mads, unrolled x4");
+        hipMemcpy(o11, dout, 256, hipMemcpyDeviceToHost);
+        same = 1;
+        for (int i = 0; i < 64; i++) same &= o10[i] == o11[i];
+        printf("V12 results %s V10's\n", same ? "equal" : "DIFFER FROM");
+        run(k_loop<13>, "V13 one-sided test, mad + sub, unrolled x4");
+        run(k_loop<14>, "V14 one-sided test, scalar threshold, x4");
+        run(k_loop<15>, "V15 V10 without its two s_add (timing)");
+        run(k_loop<16>, "V16 V10 with four s_add");
+        run(k_loop<17>, "V17 V10, its two s_add behind the v_cmp");
+        hipMemcpy(o11, dout, 256, hipMemcpyDeviceToHost);
+        same = 1;
+        for (int i = 0; i < 64; i++) same &= o10[i] == o11[i];
+        printf("V17 results %s V10's\n", same ? "equal" : "DIFFER FROM");
+        run(k_loop<11>, "V11 v_cmpx + readfirstlane, unrolled x4");
+    }
     // s_memtime frequency: compare against wall clock
     hipEvent_t a, b;
     hipEventCreate(&a);

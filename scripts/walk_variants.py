@@ -4,7 +4,8 @@ C4: 64 Mi IQ -> IIR -> resampler -> AGC, 1.61 M samples) is demodulated by a
 fresh AmpModem per variant, 5 calls, walker time averaged over calls 2-5.
 LDSP_WALK_VARIANT (the block-loop asm, walk_asm_loop<VAR / 32>): 0 product, 32 no
 repairs, 64 no per-lane-block store (32 and 64 give wrong outputs: timing only), 96
-the store issued by a helper wave's scratch slot (timing only)."""
+the store issued by a helper wave's scratch slot (timing only), 128 round 4's
+lane-block order, 160 the scalar accumulators in front of the compare (both bitwise)."""
 import json
 import os
 import sys
