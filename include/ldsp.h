@@ -377,6 +377,13 @@ int ldsp_ampmodem_walk_active(ldsp_ampmodem_t q, uint64_t *ticks, uint64_t *coun
  * are redone sample by sample -- the tests use it to exercise that path.
  * Returns the previous setting. */
 int ldsp_debug_pll_margin(int log2_b);
+/* Test hook, no reference counterpart, needs no GPU: the interval fields of one
+ * walker entry record as the entry kernel computes them (the same inline function).
+ * u: position in the table cell (22 bits); margin B; left_gap / right_gap: the gap
+ * to the previous / next entry is non-empty; dk2: a repair's step.  out[0..3] =
+ * lo (as uint32), W, amin, awidth: with x = f - lo, no event iff x <=u W, and the
+ * walker's test over all lanes passes iff x <=u W or x - amin <=u awidth. */
+int ldsp_debug_walk_fold(uint32_t u, int32_t b, int left_gap, int right_gap, uint32_t dk2, uint32_t out[4]);
 /* Test hook, no reference counterpart: the bound of an early-dispatched
  * walker's wait for the previous call's PLL state (10 ns ticks; 0 restores the
  * default 1 s), and a skew added to the epoch the object's next walker waits for

@@ -2546,6 +2546,17 @@ int ldsp_debug_pll_margin(int log2_b)
     return k::pll_margin_override(log2_b);
 }
 
+int ldsp_debug_walk_fold(uint32_t u, int32_t b, int left_gap, int right_gap, uint32_t dk2, uint32_t out[4])
+{
+    if (!out || u >= (1u << 22) || b < 1 || b > (1 << 21)) return LDSP_EINVAL;
+    const k::WalkFold f = k::pll_walk_fold(u, b, left_gap != 0, right_gap != 0, dk2);
+    out[0] = (uint32_t)f.lo;
+    out[1] = f.W;
+    out[2] = f.amin;
+    out[3] = f.awidth;
+    return LDSP_OK;
+}
+
 int ldsp_ampmodem_walk_stats(ldsp_ampmodem_t q, uint64_t* entries, uint64_t* repairs, uint64_t* fallbacks)
 {
     return guard([&] {

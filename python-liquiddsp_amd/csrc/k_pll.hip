@@ -301,7 +301,7 @@ LDSP_KERNEL_PAIR(k_pll_seqc, PllSeqcArgs, k_pll_seqc_run, 256)
 constexpr int kBlkE = 512;        // walker block: entries
 struct CandBuf {
     uint32_t* rw;         // [npad] candidate phase word w = theta + 2^21 per sample
-    uint32_t* eout;       // [nblkE][kBlkE] candidate output at each entry (the undo of a failed walker block)
+    uint32_t* eout;       // [nblkE][kBlkE] candidate output at each entry (the undo of a failed walker block: tuning-build loops that store on the walker)
     uint32_t* cs;         // [nchc][2] candidate state at chunk start
     uint32_t* ce;         // [nchc][2] candidate state at chunk end
     uint32_t* cnt;        // [nchc] entries per chunk
@@ -821,15 +821,17 @@ LDSP_KERNEL_PAIR(k_pll_scan, PllScanArgs, k_pll_scan_run, kScanT)
 
 // Entry records, one wave per chunk (4 samples per lane).  Per entry (SoA per
 // walker block: E0[kBlkE], E1[kBlkE]), with srel = s - S_blk (< 2^17):
-//   E0 = (c, W, srel, L' - dk2)
+//   E0 = (c, W, srel, amin)
 //        x = c + Kb + srel D = f(s) - lo; event iff x > W, [lo, lo + W] being
 //        the no-repair interval of f cut to [-B, B] when a neighbouring gap is
 //        non-empty (the gap to the previous / next entry)
-//   E1 = (dk1, dk2 - srel dk1, out, span) for the one crossing direction possible
-//        while |f| < 2^21 (up if u >= 2^21, else down); the repair was right iff
-//        x_post - L' <= span (see below), i.e. x_pre - (L' - dk2) <= span with the
-//        offset before the repair (x_post = x_pre + dk2), which the walker keeps.
-// The tail of the last walker block is padded with W = ~0 (never an event).
+//   E1 = (dk1, dk2 - srel dk1, out, awidth) for the one crossing direction possible
+//        while |f| < 2^21 (up if u >= 2^21, else down).  A repaired lane keeps its
+//        pre-repair x (> W), and the repair was right iff that lay in the accepted
+//        interval: x - amin <= awidth (pll_walk_fold, kernels.hpp), tested on the
+//        lanes with x > W.
+// The tail of the last walker block is padded with W = ~0 (never an event, never
+// a repaired lane).
 __device__ __forceinline__ void k_pll_entries_body(PllIn in, const AmpState* st, CandBuf cb, long n)
 {
     LDSP_LATENCY_CRITICAL();
@@ -869,11 +871,6 @@ __device__ __forceinline__ void k_pll_entries_body(PllIn in, const AmpState* st,
         const uint32_t srel = (uint32_t)(s - (long)cb.bbase[blk]);
         const uint32_t w = R0[r], u = w & 0x3fffffu;
         const uint32_t A = pth + (uint32_t)s * pd;
-        int lo = -(int)u, hi = (1 << 22) - 1 - (int)u;
-        if (lne || rne) {
-            lo = max(lo, -B);
-            hi = min(hi, B);
-        }
         const bool up = u >= (1u << 21);
         // the loop at the neighbouring table index (one cell up or down) minus the
         // candidate's own step (re-evaluated here from the same inputs: the same bits
@@ -886,33 +883,18 @@ __device__ __forceinline__ void k_pll_entries_body(PllIn in, const AmpState* st,
         const uint32_t dk1 = kn.k1 - kc.k1, dk2 = kn.k2 - kc.k2;
         const uint32_t out = __float_as_uint(kn.out);
         cb.eout[(size_t)blk * kBlkE + idx] = __float_as_uint(kc.out);
-        // A repair here is right iff f_pre (the offset before it) lies in the
-        // intersection of: the presumed one-cell crossing, [-B, B] if the left gap
-        // is non-empty, and [-B - dk2, B - dk2] (f_post within B) if the right one
-        // is.  All three are small signed intervals, so their intersection is one,
-        // checked on the walker's snapshot x_post = f_pre - lo + dk2.
-        long fl = up ? (1l << 22) - (long)u : -(1l << 22) - (long)u;
-        long fh = fl + (1l << 22) - 1;
-        if (lne) {
-            fl = max(fl, (long)-B);
-            fh = min(fh, (long)B);
-        }
-        if (rne) {
-            const long d2 = (long)(int)dk2;
-            fl = max(fl, -(long)B - d2);
-            fh = min(fh, (long)B - d2);
-        }
-        const uint32_t Lp = fl <= fh ? (uint32_t)(fl - lo) + dk2 : 0x80000000u;   // empty: always redo
-        const uint32_t span = fl <= fh ? (uint32_t)(fh - fl) : 0u;
+        const WalkFold wf = pll_walk_fold(u, B, lne, rne, dk2);
         uint4* E = cb.ent + (size_t)blk * 2 * kBlkE;
-        // stored as L' - dk2: the walker tests its pre-repair snapshot, x_pre = x_post - dk2
-        E[idx] = make_uint4(A - (uint32_t)lo, (uint32_t)(hi - lo), srel, Lp - dk2);
-        E[kBlkE + idx] = make_uint4(dk1, dk2 - srel * dk1, out, span);
+        E[idx] = make_uint4(A - (uint32_t)wf.lo, wf.W, srel, wf.amin);
+        E[kBlkE + idx] = make_uint4(dk1, dk2 - srel * dk1, out, wf.awidth);
     }
     if (k == cb.nchc - 1) {              // pad the last walker block: events never fire there
         const uint32_t ne = e, end = (ne + kBlkE - 1) / kBlkE * kBlkE;
-        for (uint32_t t = ne + lane; t < end; t += 64)
-            cb.ent[(size_t)(t / kBlkE) * 2 * kBlkE + t % kBlkE] = make_uint4(0u, ~0u, 0u, 0u);
+        for (uint32_t t = ne + lane; t < end; t += 64) {
+            uint4* E = cb.ent + (size_t)(t / kBlkE) * 2 * kBlkE + t % kBlkE;
+            E[0] = make_uint4(0u, ~0u, 0u, 0u);           // W = ~0: never an event
+            E[kBlkE] = make_uint4(0u, 0u, 0u, 0u);        // read by the walker beside E0: no stale bits
+        }
     }
 }
 
@@ -1203,14 +1185,14 @@ __device__ __forceinline__ void walk_lb(const uint4& E0, const uint4& E1, int nv
                 const uint32_t dk1 = rl(E1.x, j), dk2p = rl(E1.y, j);
                 const unsigned long long bit = 1ull << j;
                 PM |= bit;
-                xpost = sel_lane(xpost, x, bit);          // pre-repair offset (E0.w = L' - dk2)
+                xpost = sel_lane(xpost, x, bit);          // pre-repair offset, tested below
                 x = mad_lane<F24>(sx, dk1, x) + dk2p;
                 D += dk1;
                 Kb += dk2p;
                 mask = __builtin_amdgcn_ballot_w64(x > E0.y) & ((~0ull << j) << 1);
             } while (mask != 0);
         }
-        // every repaired lane: x_pre - (L' - dk2) <= span (E0.w, E1.w: k_pll_entries)
+        // every repaired lane: x_pre - amin <= awidth (E0.w, E1.w: pll_walk_fold)
         unsigned long long bad = __builtin_amdgcn_ballot_w64(xpost - E0.w > E1.w) & PM;
         if (STATS && cb.dbg == 2) bad = 1;
         if (__builtin_expect(bad != 0, 0)) {
@@ -1405,8 +1387,12 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
 // block's start in kb0 / d0 / nrep0), the rebase Kb += (S_{c+1} - S_c) D, the
 // barrier with the loader waves and the slot bookkeeping, all on SALU.  The
 // loaders guarantee blocks c + 1 and c + 2 landed at the barrier ending block c.
-// Repaired outputs are stored at y + 4 (S + srel) through a 32-bit offset
-// (n < 2^30 PCM samples per call, checked on the host).
+// The block's final offsets go to xbuf[c & 1] (the s_waitcnt lgkmcnt(0) before the
+// barrier covers the writes), from which the loaders store its repaired outputs and
+// count its repairs during block c + 1 (walk_help): nrep / nrep0 only carry the count
+// of the blocks redone in C++ through the loop.  The tuning build's loops that store
+// on the walker do so at y + 4 (S + srel) through a 32-bit offset (n < 2^30 PCM
+// samples per call, checked on the host).
 #define WL_PF(A, B, OFS_A, OFS_B)                                                                           \
     "ds_read_b128 v[" #A "], %[ln] offset:" #OFS_A "\n\t"                                                  \
     "ds_read_b128 v[" #B "], %[ln] offset:" #OFS_B "\n\t"
@@ -1420,7 +1406,7 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
 // behind it they issue during the wait for VCC that the branch has anyway
 // (scripts/ubench/walk_loop.hip V10 against V15 / V17).  Lane j itself keeps its
 // pre-repair offset, so after the loop the repaired lanes are exactly those whose x
-// is still > W (PM), and the interval test reads x_pre - (L' - dk2) <= span (E0.w).
+// is still > W, and the interval test reads x - amin <= awidth (E0.w, E1.w) on them.
 // No snapshot, no PM bookkeeping, no next-lane-block update inside the loop: the next
 // lane-block's offsets are formed once from the final Kb, D (v_mul_lo + v_add3) and
 // its events compared into VCC before this lane-block's store / test, which hide the
@@ -1448,13 +1434,42 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "s_add_u32 %[d], %[d], %[dk1]\n\t"                                                                     \
     "v_cmp_gt_u32_e32 vcc, " X ", " W "\n\t"
 #endif
-// The lane-block transition: the next lane-block's offsets (v_mul_lo, quarter
-// rate, then v_add3) are the critical path into its VCCZ branch, so the
-// independent work -- this lane-block's repaired mask, store offset and interval
-// test -- is issued between the multiply and the add and the store between the
-// add and the compare, instead of after them (in-order issue: an instruction
-// waiting on a result holds every later one).
-#define WL_LB(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, TAIL)                           \
+// The lane-block transition.  The walker carries the serial chain and nothing else:
+// the next lane-block's offsets (v_mul_lo, quarter rate, then v_add3) are the critical
+// path into its VCCZ branch, so this lane-block's interval test -- sat((x - amin) -
+// awidth), kept in the lanes with x > W by a minimum with sat(x - W) (plain VALU: no
+// mask register, no exec switch) -- and the write of its final
+// offsets to xbuf[c & 1][lane-block][lane] are issued between the multiply and the add
+// (in-order issue: an instruction waiting on a result holds every later one).  The
+// repaired outputs are stored and the repairs counted from xbuf by the loader waves
+// one block later (walk_help): no store offset, exec switch, store or count here.
+#define WL_LB(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)                           \
+    "s_cbranch_vccz 2f\n"                                                                                  \
+    "1:\n\t"                                                                                               \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccnz 1b\n"                                                    \
+    "3:\n\t"                                                                                               \
+    "s_mov_b64 exec, -1\n"                                                                                 \
+    "2:\n\t"                                                                                               \
+    "v_mul_lo_u32 %[t2], %[d], " SXN "\n\t"                                                                \
+    "v_sub_u32_e64 %[off], " X ", " E0Y " clamp\n\t"                                                       \
+    "v_sub_u32 %[t], " X ", " E0W "\n\t"                                                                   \
+    "v_sub_u32_e64 %[t], %[t], " E1W " clamp\n\t"                                                          \
+    "v_min_u32 %[t], %[t], %[off]\n\t"                                                                     \
+    "v_or_b32 %[acc], %[acc], %[t]\n\t"                                                                    \
+    "ds_write_b32 %[xs], " X " offset:" XO "\n\t"                                                          \
+    "v_add3_u32 " XN ", " N0X ", %[kb], %[t2]\n\t"                                                         \
+    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t" TAIL
+// block end: the other half of xbuf for the next block
+#define WL_XFLIP "v_sub_u32 %[xs], %[xsum], %[xs]\n\t"
+#define WL_NOFLIP ""
+#ifdef LDSP_TUNING
+// The walker that stores and counts itself, as before the helper waves (bitwise A/B:
+// k_pll_walk VAR 288): the repaired mask, store offset and masked interval test
+// between the multiply and the add, the store between the add and the compare.
+#define WL_LB_PARENT(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)                           \
     "s_cbranch_vccz 2f\n"                                                                                  \
     "1:\n\t"                                                                                               \
     WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
@@ -1477,9 +1492,8 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t"                                                            \
     "s_bcnt1_i32_b64 %[nr], %[pm]\n\t"                                                                     \
     "s_add_u32 %[nrep], %[nrep], %[nr]\n\t" TAIL
-#ifdef LDSP_TUNING
-// The product lane-block around WX_REP_PRE (k_pll_walk VAR 160)
-#define WL_LB_PRE(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, TAIL)                           \
+// The parent's lane-block around WX_REP_PRE (k_pll_walk VAR 160)
+#define WL_LB_PRE(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)                           \
     "s_cbranch_vccz 2f\n"                                                                                  \
     "1:\n\t"                                                                                               \
     WX_REP_PRE(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                              \
@@ -1503,7 +1517,7 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "s_bcnt1_i32_b64 %[nr], %[pm]\n\t"                                                                     \
     "s_add_u32 %[nrep], %[nrep], %[nr]\n\t" TAIL
 // Round 4's lane-block order (timing A/B against WL_LB: k_pll_walk VAR 128)
-#define WL_LB_ORIG(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, TAIL)                           \
+#define WL_LB_ORIG(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)                           \
     "s_cbranch_vccz 2f\n"                                                                                  \
     "1:\n\t"                                                                                               \
     WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
@@ -1529,7 +1543,7 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
 // Timing variants of the product loop (tuning build, k_pll_walk VAR 32 / 64; wrong
 // outputs): NOREP skips every repair loop (the lane-block transitions, stores and
 // tests alone), NOST drops the store / interval test / repair count (loop + transitions).
-#define WL_LB_NOREP(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, TAIL)                     \
+#define WL_LB_NOREP(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)                     \
     "s_branch 2f\n"                                                                                        \
     "2:\n\t"                                                                                               \
     "v_mul_lo_u32 %[t], %[d], " SXN "\n\t"                                                                 \
@@ -1544,7 +1558,7 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "s_mov_b64 exec, -1\n\t"                                                                               \
     "s_bcnt1_i32_b64 %[nr], %[pm]\n\t"                                                                     \
     "s_add_u32 %[nrep], %[nrep], %[nr]\n\t" TAIL
-#define WL_LB_NOST(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, TAIL)                      \
+#define WL_LB_NOST(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)                      \
     "s_cbranch_vccz 2f\n"                                                                                  \
     "1:\n\t"                                                                                               \
     WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
@@ -1557,10 +1571,13 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "v_mul_lo_u32 %[t], %[d], " SXN "\n\t"                                                                 \
     "v_add3_u32 " XN ", " N0X ", %[kb], %[t]\n\t"                                                          \
     "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t" TAIL
-// HELPER: the walker's side of a design where other waves store the repaired
-// outputs and count the repairs: the repaired lanes' test via a select (no exec
-// switch), the offsets written to LDS for the helpers (timing only: one junk slot)
-#define WL_LB_HELPER(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, TAIL)                    \
+// HELPER (VAR 96): the product's lane-block (WL_LB) with the loader waves' deferred
+// work left out -- what the helpers' LDS reads and stores cost the walker.  Timing
+// only: no repaired output is stored, no repair counted.
+// NOTEST (VAR 192): the same without any interval test in the transition (multiply,
+// offsets to xbuf, add, compare) -- the bound of a design whose verdict lags the
+// walker altogether.  Timing only.
+#define WL_LB_NOTEST(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)                    \
     "s_cbranch_vccz 2f\n"                                                                                  \
     "1:\n\t"                                                                                               \
     WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
@@ -1570,20 +1587,37 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "3:\n\t"                                                                                               \
     "s_mov_b64 exec, -1\n"                                                                                 \
     "2:\n\t"                                                                                               \
-    "v_mul_lo_u32 %[t], %[d], " SXN "\n\t"                                                                 \
-    "v_add3_u32 " XN ", " N0X ", %[kb], %[t]\n\t"                                                          \
-    "v_cmp_gt_u32_e64 %[pm], " X ", " E0Y "\n\t"                                                           \
+    "v_mul_lo_u32 %[t2], %[d], " SXN "\n\t"                                                                \
+    "ds_write_b32 %[xs], " X " offset:" XO "\n\t"                                                          \
+    "v_add3_u32 " XN ", " N0X ", %[kb], %[t2]\n\t"                                                         \
+    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t" TAIL
+// The transitions of the two alone, every repair loop skipped as in NOREP (VAR 224 /
+// 256: with VAR 32 the account of ns per transition before and after; the state is
+// garbage without the repairs, so the test's result goes to a junk register)
+#define WL_LB_HELPER_NOREP(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)              \
+    "s_branch 2f\n"                                                                                        \
+    "2:\n\t"                                                                                               \
+    "v_mul_lo_u32 %[t2], %[d], " SXN "\n\t"                                                                \
+    "v_sub_u32_e64 %[off], " X ", " E0Y " clamp\n\t"                                                       \
     "v_sub_u32 %[t], " X ", " E0W "\n\t"                                                                   \
     "v_sub_u32_e64 %[t], %[t], " E1W " clamp\n\t"                                                          \
-    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t"                                                            \
-    "v_cndmask_b32_e64 %[t], 0, %[t], %[pm]\n\t"                                                           \
-    "v_or_b32 %[acc], %[acc], %[t]\n\t"                                                                    \
-    "ds_write_b32 %[xs], " X "\n\t" TAIL
+    "v_min_u32 %[t], %[t], %[off]\n\t"                                                                     \
+    "v_or_b32 v165, v165, %[t]\n\t"                                                                        \
+    "ds_write_b32 %[xs], " X " offset:" XO "\n\t"                                                          \
+    "v_add3_u32 " XN ", " N0X ", %[kb], %[t2]\n\t"                                                         \
+    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t" TAIL
+#define WL_LB_NOTEST_NOREP(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)              \
+    "s_branch 2f\n"                                                                                        \
+    "2:\n\t"                                                                                               \
+    "v_mul_lo_u32 %[t2], %[d], " SXN "\n\t"                                                                \
+    "ds_write_b32 %[xs], " X " offset:" XO "\n\t"                                                          \
+    "v_add3_u32 " XN ", " N0X ", %[kb], %[t2]\n\t"                                                         \
+    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t" TAIL
 #endif
-#define WL_LBQ(LBM, a, b, c, d, e, f, g, h, n0, n1, n2, X, XN, TAIL)                                         \
-    LBM("v" #a, "v" #b, "v" #c, "v" #d, "v" #e, "v" #f, "v" #g, "v" #h, "v" #n0, "v" #n1, "v" #n2, X, XN, TAIL)
+#define WL_LBQ(LBM, a, b, c, d, e, f, g, h, n0, n1, n2, X, XN, XO, TAIL)                                         \
+    LBM("v" #a, "v" #b, "v" #c, "v" #d, "v" #e, "v" #f, "v" #g, "v" #h, "v" #n0, "v" #n1, "v" #n2, X, XN, XO, TAIL)
 
-#define WALK_ASM(LBM)                                                                                    \
+#define WALK_ASM(LBM, BEND)                                                                                  \
     asm volatile(                                                                                                     \
         /* prologue: block c's entries, block c + 1's header, LB0's offsets / events */                               \
         "v_mov_b32 %[lh], %[sn]\n\t"                                                                                  \
@@ -1615,19 +1649,19 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
         "v_add3_u32 %[xa], v100, %[kb], %[t]\n\t"                                                                     \
         "v_cmp_gt_u32_e32 vcc, %[xa], v101\n"                                                                         \
         "9:\n\t"                                                                                                      \
-        WL_LBQ(LBM, 100, 101, 102, 103, 104, 105, 106, 107, 108, 109, 110, "%[xa]", "%[xb]",                               \
+        WL_LBQ(LBM, 100, 101, 102, 103, 104, 105, 106, 107, 108, 109, 110, "%[xa]", "%[xb]", "0",                          \
                WL_PF(100:103, 104:107, 0, 8192))                                                                      \
-        WL_LBQ(LBM, 108, 109, 110, 111, 112, 113, 114, 115, 116, 117, 118, "%[xb]", "%[xa]",                               \
+        WL_LBQ(LBM, 108, 109, 110, 111, 112, 113, 114, 115, 116, 117, 118, "%[xb]", "%[xa]", "256",                        \
                WL_PF(108:111, 112:115, 1024, 9216))                                                                   \
-        WL_LBQ(LBM, 116, 117, 118, 119, 120, 121, 122, 123, 124, 125, 126, "%[xa]", "%[xb]",                               \
+        WL_LBQ(LBM, 116, 117, 118, 119, 120, 121, 122, 123, 124, 125, 126, "%[xa]", "%[xb]", "512",                        \
                WL_PF(116:119, 120:123, 2048, 10240))                                                                  \
-        WL_LBQ(LBM, 124, 125, 126, 127, 128, 129, 130, 131, 132, 133, 134, "%[xb]", "%[xa]",                               \
+        WL_LBQ(LBM, 124, 125, 126, 127, 128, 129, 130, 131, 132, 133, 134, "%[xb]", "%[xa]", "768",                        \
                WL_PF(124:127, 128:131, 3072, 11264))                                                                  \
-        WL_LBQ(LBM, 132, 133, 134, 135, 136, 137, 138, 139, 140, 141, 142, "%[xa]", "%[xb]",                               \
+        WL_LBQ(LBM, 132, 133, 134, 135, 136, 137, 138, 139, 140, 141, 142, "%[xa]", "%[xb]", "1024",                       \
                WL_PF(132:135, 136:139, 4096, 12288))                                                                  \
-        WL_LBQ(LBM, 140, 141, 142, 143, 144, 145, 146, 147, 148, 149, 150, "%[xb]", "%[xa]",                               \
+        WL_LBQ(LBM, 140, 141, 142, 143, 144, 145, 146, 147, 148, 149, 150, "%[xb]", "%[xa]", "1280",                       \
                WL_PF(140:143, 144:147, 5120, 13312))                                                                  \
-        WL_LBQ(LBM, 148, 149, 150, 151, 152, 153, 154, 155, 156, 157, 158, "%[xa]", "%[xb]",                               \
+        WL_LBQ(LBM, 148, 149, 150, 151, 152, 153, 154, 155, 156, 157, 158, "%[xa]", "%[xb]", "1536",                       \
                WL_PF(148:151, 152:155, 6144, 14336))                                                                  \
         /* lane-block 7: its N0 is the next block's lane-block 0 (read after LB 0; the */                             \
         /* header of block c + 1 was the first read of this block) */                                                 \
@@ -1636,7 +1670,7 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
         "s_sub_u32 %[dS], %[snx], %[S]\n\t"                                                                           \
         "v_add_u32 %[sx7], %[dS], v102\n\t"                                                                           \
         LBM("v156", "v157", "v158", "v159", "v160", "v161", "v162", "v163", "v100", "v101", "%[sx7]", "%[xb]",      \
-              "%[xa]", "")                                                                                            \
+              "%[xa]", "1792", "")                                                                                            \
         /* block end */                                                                                               \
         "v_cmp_ne_u32_e64 %[bad], 0, %[acc]\n\t"                                                                      \
         "s_mul_i32 %[tS], %[dS], %[d]\n\t"                                                                            \
@@ -1652,6 +1686,7 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
         "s_mov_b32 %[d0], %[d]\n\t"                                                                                   \
         "s_mov_b32 %[nrep0], %[nrep]\n\t"                                                                             \
         "v_mov_b32 %[acc], 0\n\t"                                                                                     \
+        BEND                                                                                                          \
         "s_add_u32 %[c], %[c], 1\n\t"                                                                                 \
         "s_add_u32 %[sn], %[sn], %[slot]\n\t"                                                                         \
         "s_cmp_eq_u32 %[sn], %[rend]\n\t"                                                                             \
@@ -1666,21 +1701,21 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
         "8:\n\t"                                                                                                      \
         "s_waitcnt lgkmcnt(0)"                                                                                        \
         : [xa] "=&v"(xa), [xb] "=&v"(xb), [t] "=&v"(t), [t2] "=&v"(t2), [off] "=&v"(off), [acc] "=&v"(acc),          \
-          [sx7] "=&v"(sx7), [ln] "=&v"(ln), [lh] "=&v"(lh), [s7] "+v"(s7),                                            \
+          [sx7] "=&v"(sx7), [ln] "=&v"(ln), [lh] "=&v"(lh), [s7] "+v"(s7), [xs] "+v"(xs),                                          \
           [pm] "=&s"(pm), [bad] "=&s"(bad),                                                                           \
           [kb] "+s"(kb), [d] "+s"(d), [nrep] "+s"(nrep), [c] "+s"(c), [S] "+s"(S), [Sp] "+s"(Sprev),                  \
           [kb0] "=&s"(kb0), [d0] "=&s"(d0), [nrep0] "=&s"(nrep0), [sn] "+s"(sn),                                      \
           [j] "=&s"(j), [dk1] "=&s"(dk1), [dk2] "=&s"(dk2), [nr] "=&s"(nr), [snx] "=&s"(snx), [dS] "=&s"(dS),         \
           [tS] "=&s"(tS), [s4] "=&s"(s4)                                                                              \
         : [la] "v"(la), [l16] "v"(lane16), [nblk] "s"(nblk), [ring] "s"(ring), [rend] "s"(rend), [slot] "s"(kSlot), \
-          [xs] "v"(xs),   \
+          [xsum] "v"(xsum),\
           [yb] "s"(y)                                                                                                 \
         : "scc", "vcc", "exec", "memory", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109",\
           "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122",     \
           "v123", "v124", "v125", "v126", "v127", "v128", "v129", "v130", "v131", "v132", "v133", "v134", "v135",     \
           "v136", "v137", "v138", "v139", "v140", "v141", "v142", "v143", "v144", "v145", "v146", "v147", "v148",     \
           "v149", "v150", "v151", "v152", "v153", "v154", "v155", "v156", "v157", "v158", "v159", "v160", "v161",     \
-          "v162", "v163", "v164");
+          "v162", "v163", "v164", "v165");
 
 struct WalkLoop {
     uint32_t c, kb, d, nrep;          // block index; offset model; live repair count
@@ -1690,12 +1725,14 @@ struct WalkLoop {
 };
 
 // Runs blocks c .. nblk - 1 until one fails its interval test (returns with c = that
-// block, not yet barriered) or all are done (c = nblk).  PV: 0 the product, 1 / 2 the
-// tuning build's timing variants (WL_LB_NOREP / WL_LB_NOST), 4 / 5 earlier orders
-// (WL_LB_ORIG / WL_LB_PRE).
+// block, not yet barriered) or all are done (c = nblk).  xb0: this lane's word of
+// xbuf[0][0].  PV: 0 the product; the tuning build's variants: 1 / 2 WL_LB_NOREP /
+// WL_LB_NOST, 3 the product's loop (without the helpers' work), 4 / 5 / 9 earlier loops
+// that store and count on the walker (WL_LB_ORIG / WL_LB_PRE / WL_LB_PARENT), 6 - 8
+// WL_LB_NOTEST / WL_LB_HELPER_NOREP / WL_LB_NOTEST_NOREP.
 template <int PV>
 __device__ __forceinline__ void walk_asm_loop(WalkLoop& w, uint32_t nblk, uint32_t ring, float* y, uint32_t lane16,
-                                              uint32_t xs = 0)
+                                              uint32_t xb0)
 {
     constexpr uint32_t kSlot = (uint32_t)sizeof(WalkBufE);
     static_assert(sizeof(WalkBufE) == 16400, "slot stride below");
@@ -1703,23 +1740,33 @@ __device__ __forceinline__ void walk_asm_loop(WalkLoop& w, uint32_t nblk, uint32
     const uint32_t la = ring + (w.c % kRing) * kSlot + lane16;        // block c's entries (prologue)
     uint32_t sn = ring + ((w.c + 1) % kRing) * kSlot;                  // slot of block c + 1
     uint32_t xa, xb, t, t2, off, acc, sx7, ln, lh, s7 = w.s7;
+    uint32_t xs = xb0 + ((w.c & 1u) << 11);                            // xbuf[c & 1][0][lane]
+    const uint32_t xsum = 2u * xb0 + 2048u;
     uint32_t j, dk1, dk2, nr, snx, dS, tS, s4;
     unsigned long long pm, bad;
     uint32_t kb = w.kb, d = w.d, nrep = w.nrep, c = w.c, S = w.S, Sprev = w.Sprev, kb0, d0, nrep0;
     if constexpr (PV == 0) {
-        WALK_ASM(WL_LB);
+        WALK_ASM(WL_LB, WL_XFLIP);
     }
 #ifdef LDSP_TUNING
     else if constexpr (PV == 1) {
-        WALK_ASM(WL_LB_NOREP);
+        WALK_ASM(WL_LB_NOREP, WL_NOFLIP);
     } else if constexpr (PV == 2) {
-        WALK_ASM(WL_LB_NOST);
+        WALK_ASM(WL_LB_NOST, WL_NOFLIP);
     } else if constexpr (PV == 4) {
-        WALK_ASM(WL_LB_ORIG);
+        WALK_ASM(WL_LB_ORIG, WL_NOFLIP);
     } else if constexpr (PV == 5) {
-        WALK_ASM(WL_LB_PRE);
+        WALK_ASM(WL_LB_PRE, WL_NOFLIP);
+    } else if constexpr (PV == 3) {
+        WALK_ASM(WL_LB, WL_XFLIP);
+    } else if constexpr (PV == 6) {
+        WALK_ASM(WL_LB_NOTEST, WL_XFLIP);
+    } else if constexpr (PV == 7) {
+        WALK_ASM(WL_LB_HELPER_NOREP, WL_XFLIP);
+    } else if constexpr (PV == 8) {
+        WALK_ASM(WL_LB_NOTEST_NOREP, WL_XFLIP);
     } else {
-        WALK_ASM(WL_LB_HELPER);
+        WALK_ASM(WL_LB_PARENT, WL_NOFLIP);
     }
 #endif
     w.c = c;
@@ -1734,8 +1781,23 @@ __device__ __forceinline__ void walk_asm_loop(WalkLoop& w, uint32_t nblk, uint32
     w.s7 = s7;
 }
 
-// Wave 0 walks the entries of block c; waves 1-7 DMA the entries of block c + kRing - 1
-// into the LDS ring meanwhile.
+// Loader wave, product path: lane-block q of a block that passed its interval test,
+// one block later.  The repaired lanes are those whose final offset (xbuf) is still
+// an event (the repair loop leaves lane j its pre-repair x > W): their outputs go to
+// y[S + srel]; returns their number.
+__device__ __forceinline__ uint32_t walk_help(const WalkBufE& b, const uint32_t* xq, int q, int lane, float* y)
+{
+    const uint4 E0 = b.e[0][q * 64 + lane];
+    const uint32_t out = b.e[1][q * 64 + lane].z;
+    const uint32_t S = b.hdr[0];
+    const bool pm = xq[q * 64 + lane] > E0.y;
+    if (pm) y[(size_t)S + E0.z] = __uint_as_float(out);
+    return (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(pm));
+}
+
+// Wave 0 walks the entries of block c; waves 1-7 DMA the entries of a block kAhead
+// ahead into the LDS ring meanwhile and, on the product path, store the repaired
+// outputs of block c - 1 and count its repairs (walk_help), which wave 0 leaves to them.
 template <bool F24, bool STATS, int VAR = 0>
 __device__ __forceinline__ void k_pll_walk_body(PllIn in, long n, AmpState* st, CandBuf cb,
                                                            float* __restrict__ y, uint32_t wexp)
@@ -1743,9 +1805,16 @@ __device__ __forceinline__ void k_pll_walk_body(PllIn in, long n, AmpState* st, 
     LDSP_LATENCY_CRITICAL();
     __shared__ WalkBufE buf[kRing];      // ring: block c in buf[c % kRing], DMA'd kRing - 1 blocks ahead
     __shared__ float wtab[1024];         // NCO table for the fallback's full loop steps
-#ifdef LDSP_TUNING
-    __shared__ uint32_t xscratch[64];    // timing variant 96 (WL_LB_HELPER) writes its offsets here
-#endif
+    __shared__ uint32_t xbuf[2][kBlkE / 64][64];   // block c's final offsets in xbuf[c & 1], for walk_help
+    __shared__ uint32_t redone[2];       // [c & 1] = c + 1: block c was redone by wave 0, nothing deferred
+    __shared__ uint32_t hcount;          // repairs counted by the loader waves
+    // the product path's loop stores and counts on the loader waves (HELP); earlier
+    // loops of the tuning build on the walker (WSTORE), the timing-only ones nowhere
+    constexpr bool HELP = F24 && !STATS && VAR == 0;
+    constexpr bool WSTORE = VAR == 32 || VAR == 64 || VAR == 128 || VAR == 160 || VAR == 288;
+    // HELP reads block c - 1's slot during block c, so its DMA reuses the slot of block
+    // c - 2: one block less ahead
+    constexpr long kAhead = HELP ? kRing - 2 : kRing - 1;
     // Own the CU: 8 waves x 256 VGPRs fill every SIMD's register file, so no wave of
     // the kernels running beside the walk (the next call's AGC, candidates, ...)
     // is placed on the walker's SIMD and takes issue slots from its serial chain.
@@ -1757,10 +1826,12 @@ __device__ __forceinline__ void k_pll_walk_body(PllIn in, long n, AmpState* st, 
     const uint32_t NE = rfl(*(volatile uint32_t*)cb.ne);
     const long nblk = ((long)NE + kBlkE - 1) / kBlkE;
     if (wave != 0) {
-        for (long b0 = 0; b0 < kRing - 1 && b0 < nblk; b0++) walk_dma(buf[b0], cb, b0, lw, lane);
-        // blocks 0 and 1 landed: at most the DMAs of blocks 2 .. kRing - 2 still in flight
-        vm_wait_blocks(min(5l, nblk - 2));
+        for (long b0 = 0; b0 < kAhead && b0 < nblk; b0++) walk_dma(buf[b0], cb, b0, lw, lane);
+        // blocks 0 and 1 landed: at most the DMAs of blocks 2 .. kAhead - 1 still in flight
+        vm_wait_blocks(min(kAhead - 2, nblk - 2));
     }
+    if (tid < 2) redone[tid] = 0u;
+    if (tid == 2) hcount = 0u;
     for (int i = tid; i < 1024; i += kWalkThreads) wtab[i] = in.table[i];
     __syncthreads();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1816,19 +1887,36 @@ __device__ __forceinline__ void k_pll_walk_body(PllIn in, long n, AmpState* st, 
 #ifdef LDSP_TUNING
     unsigned long long cyc_undo = 0, cyc_fb = 0;      // product loop's block redos: undo pass, fallback lane-blocks
 #endif
-    static_assert(VAR == 0 || VAR == 32 || VAR == 64 || VAR == 96 || VAR == 128 || VAR == 160, "walker variant");
+    static_assert(VAR == 0 || VAR == 32 || VAR == 64 || VAR == 96 || VAR == 128 || VAR == 160 || VAR == 192 ||
+                      VAR == 224 || VAR == 256 || VAR == 288,
+                  "walker variant");
     if constexpr (F24 && !STATS) {
         // the product path: the block loop in one asm statement (walk_asm_loop)
         if (wave != 0) {
-            for (long c = 0; c < nblk; c++) {
-                // slot (c + kRing - 1) % kRing held block c - 1, released by the previous barrier
-                if (c + kRing - 1 < nblk) walk_dma(buf[(c + kRing - 1) % kRing], cb, c + kRing - 1, lw, lane);
+            // Every wave executes one barrier per block (wave 0: the asm loop's or the
+            // redo's), then HELP's final one.  Between the barriers ending blocks c - 1 and
+            // c, wave 0 writes xbuf[c & 1] and redone[c & 1] and the loaders read
+            // xbuf[(c - 1) & 1], redone[(c - 1) & 1] and block c - 1's slot, which the
+            // DMA overwrites after the barrier ending block c at the earliest.
+            uint32_t hrep = 0;
+            for (long c = 0; c <= nblk; c++) {
+                if (HELP && c > 0 && rfl(*(volatile uint32_t*)&redone[(c - 1) & 1]) != (uint32_t)c) {
+                    const WalkBufE& pb = buf[(c - 1) % kRing];
+                    const uint32_t* xq = &xbuf[(c - 1) & 1][0][0];
+                    hrep += walk_help(pb, xq, lw, lane, y);
+                    if (lw == 0) hrep += walk_help(pb, xq, kLoadWaves, lane, y);
+                }
+                if (c == nblk) break;
+                // slot (c + kAhead) % kRing held block c + kAhead - kRing, released by the previous barrier
+                if (c + kAhead < nblk) walk_dma(buf[(c + kAhead) % kRing], cb, c + kAhead, lw, lane);
                 // blocks c + 1 and c + 2 must have landed before the barrier ending block c
-                vm_wait_blocks(min(5l, nblk - c - 3));
+                // (the loaders' stores count in vmcnt too: the wait is then longer, never shorter)
+                vm_wait_blocks(min(kAhead - 2, nblk - c - 3));
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
             }
+            if (HELP && lane == 0) atomicAdd(&hcount, hrep);
         } else {
             WalkLoop w{0u, rfl(g.Kb), rfl(g.D), 0u, 0u, 0u, 0u, 0u, 0u, 0u};
             const uint32_t ring = (uint32_t)(uintptr_t)&buf[0];
@@ -1837,27 +1925,25 @@ __device__ __forceinline__ void k_pll_walk_body(PllIn in, long n, AmpState* st, 
                 const uint32_t Sn = rfl(buf[c0 % kRing].hdr[0]);
                 w.kb += (Sn - w.S) * w.d;
                 w.S = Sn;
-#ifdef LDSP_TUNING
                 walk_asm_loop<VAR / 32>(w, (uint32_t)nblk, ring, y, (uint32_t)lane * 16u,
-                                        (uint32_t)(uintptr_t)&xscratch[lane]);
-#else
-                walk_asm_loop<VAR / 32>(w, (uint32_t)nblk, ring, y, (uint32_t)lane * 16u);
-#endif
+                                        (uint32_t)(uintptr_t)&xbuf[0][0][lane]);
                 if (w.c > c0) prev = PrevLB{w.s7, 64, w.Sprev, false};
                 if (w.c >= (uint32_t)nblk) break;
 #ifdef LDSP_TUNING
                 const unsigned long long tf0 = wall_clock64();      // fallback cost (stats[2], stats[3])
 #endif
-                // block c failed its interval test: undo its speculative stores (the
-                // candidates' outputs at every entry), then redo it lane-block by
-                // lane-block from its entry state (each rewrite lands after the previous one)
+                // block c failed its interval test: redo it lane-block by lane-block from
+                // its entry state (each rewrite lands after the previous one).  Its repaired
+                // outputs were never stored (redone[]: the loaders skip the block); a loop
+                // that stores on the walker (tuning build) first undoes them with the
+                // candidates' outputs at every entry.
                 const long c = w.c;
                 const WalkBufE& b = buf[c % kRing];
                 const int cnt = (int)min((long)kBlkE, (long)NE - c * kBlkE);
                 S = w.S;
                 float* yb = y + S;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                {
+                if constexpr (WSTORE) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     // every load first (one round trip), then the stores
                     uint32_t sr[kBlkE / 64], cw[kBlkE / 64];
 #pragma unroll
@@ -1868,8 +1954,9 @@ __device__ __forceinline__ void k_pll_walk_body(PllIn in, long n, AmpState* st, 
 #pragma unroll
                     for (int q = 0; q < kBlkE / 64; q++)
                         if (q * 64 + lane < cnt) y[S + sr[q]] = __uint_as_float(cw[q]);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (lane == 0) *(volatile uint32_t*)&redone[c & 1] = (uint32_t)c + 1u;
 #ifdef LDSP_TUNING
                 const unsigned long long tu1 = wall_clock64();
                 cyc_undo += tu1 - tf0;
@@ -1908,6 +1995,13 @@ __device__ __forceinline__ void k_pll_walk_body(PllIn in, long n, AmpState* st, 
             g.D = w.d;
             g.nrep = w.nrep;
             S = w.S;
+        }
+        if constexpr (HELP) {
+            // the loaders' repair counts (wave 0's own are those of its redone blocks)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            g.nrep += *(volatile uint32_t*)&hcount;
         }
     }
     for (long c = 0; c < ((F24 && !STATS) ? 0 : nblk); c++) {
@@ -2228,6 +2322,10 @@ void pll_back(const PllCall& c, hipStream_t s)
                 case 96: WALK_LAUNCH(true, false, 96); break;
                 case 128: WALK_LAUNCH(true, false, 128); break;
                 case 160: WALK_LAUNCH(true, false, 160); break;
+                case 192: WALK_LAUNCH(true, false, 192); break;
+                case 224: WALK_LAUNCH(true, false, 224); break;
+                case 256: WALK_LAUNCH(true, false, 256); break;
+                case 288: WALK_LAUNCH(true, false, 288); break;
                 default: break;
                 }
                 return;

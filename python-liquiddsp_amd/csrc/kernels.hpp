@@ -300,6 +300,56 @@ int pll_margin_override(int log2_b);       // diagnostics: 0 = default; returns 
 // reads and advances the true state, so it must follow the previous call's back half.
 void pll_back(const PllCall& c, hipStream_t s);
 
+// The interval fields of one walker entry record (k_pll_entries; host-callable so the
+// CPU suite runs the kernel's own code: ldsp_debug_walk_fold).  u: the candidate's
+// position in its table cell (22 bits), so the offset f of the true phase from the
+// candidate's stays in the cell while f in [-u, 2^22 - 1 - u]; B: the margin; lne / rne:
+// the gap to the previous / next entry is non-empty (|f| <= B needed across it); dk2:
+// what a repair at this entry adds to f.
+//   [lo, lo + W]: no event (the cell, cut to [-B, B] if lne or rne); the walker's
+//       x = f - lo, event iff x >u W.
+//   [fl, fh]: the pre-repair offsets at which a repair here is right -- the one
+//       crossing possible while |f| < 2^21 (up if u >= 2^21, else down), cut to [-B, B]
+//       if lne and to [-B - dk2, B - dk2] (f_post within B) if rne.
+//   A repaired lane keeps its pre-repair x, so the walker's test over every lane is
+//   x <=u W (not repaired) or x - amin <=u awidth (repaired, and rightly).  [fl, fh]
+//   mostly starts where the cell ends (up: fl = hi + 1; down: fh = lo - 1), but not
+//   always -- with only rne, the cell's side towards the crossing cut to +-B and dk2
+//   pointing back inside it lies detached beyond a gap that must fail -- so the two
+//   intervals are not folded into one.  An empty [fl, fh] is stored as amin = awidth
+//   = 0: x = 0 is never a repaired lane's, so every repair at the entry fails.
+struct WalkFold {
+    int32_t lo;
+    uint32_t W, amin, awidth;
+};
+__host__ __device__ inline WalkFold pll_walk_fold(uint32_t u, int32_t B, bool lne, bool rne, uint32_t dk2)
+{
+    long lo = -(long)u, hi = (1l << 22) - 1 - (long)u;
+    if (lne || rne) {
+        lo = lo > -(long)B ? lo : -(long)B;
+        hi = hi < (long)B ? hi : (long)B;
+    }
+    const bool up = u >= (1u << 21);
+    long fl = up ? (1l << 22) - (long)u : -(1l << 22) - (long)u;
+    long fh = fl + (1l << 22) - 1;
+    if (lne) {
+        fl = fl > -(long)B ? fl : -(long)B;
+        fh = fh < (long)B ? fh : (long)B;
+    }
+    if (rne) {
+        const long d2 = (long)(int32_t)dk2;
+        fl = fl > -(long)B - d2 ? fl : -(long)B - d2;
+        fh = fh < (long)B - d2 ? fh : (long)B - d2;
+    }
+    const bool any = fl <= fh;
+    WalkFold r;
+    r.lo = (int32_t)lo;
+    r.W = (uint32_t)(hi - lo);
+    r.amin = any ? (uint32_t)(fl - lo) : 0u;
+    r.awidth = any ? (uint32_t)(fh - fl) : 0u;
+    return r;
+}
+
 // ------------------------------------------------------------------ debug
 void math_eval(int fn, const float* a, const float* b, float* y, size_t n, hipStream_t s);
 
