@@ -489,7 +489,47 @@ int ldsp_firhilb_execute(ldsp_firhilb_t q, const void *x, size_t n, void *y0, vo
 int ldsp_debug_firhilb_tile(int op, size_t *samples);
 
 /* ------------------------------------------------------------------------
- * Raw IQ conversion.  Replaces bytes_to_iq (src/utility.hpp:61-69,
+ * Channelizer: a polyphase analysis filter bank, one wideband complex64
+ * stream to M channel rows in one pass.  No reference counterpart (liquid's
+ * firpfbch family is the same structure); the definition is this library's
+ * own.  For the concatenated input x[t] (zeros before the first sample and
+ * after reset), a real prototype h of L taps, M channels and decimation D:
+ *   y[k][n] = scale sum_{j<L} h[j] x[nD - j] exp(-2 pi i k (nD - j) / M)
+ * i.e. mix down by k / M cycles per sample, filter with h, keep every D-th
+ * sample starting at t = 0.  Channel k is centred at k / M; k >= M / 2 are the
+ * negative frequencies (FFT order).  Output n is emitted by the call that
+ * delivers x[nD]: with T samples seen before a call and skip = (-T) mod D, a
+ * call of n samples returns n > skip ? ceil((n - skip) / D) : 0 columns; calls
+ * of any length, 0 included, are allowed.
+ *   M: a power of two, 4 <= M <= 256;  D = M (critically sampled) or M / 2 (2x
+ *   oversampled);  at most 17 taps per branch (L <= 17 M; m <= 8).
+ * ldsp_chan_create designs h = firdes_kaiser(2 M m + 1, fc, as, 0) (fc <= 0:
+ * 0.5 / M) and sets scale = 1 / sum(h) (unit gain at a channel's centre);
+ * ldsp_chan_create_taps takes h as given with scale = 1.  A non-power-of-two
+ * M, M < 4, another D, m = 0, L = 0, as <= 0 and fc >= 0.5 are LDSP_EINVAL; a
+ * power-of-two M above 256 and more than 17 taps per branch are LDSP_EUNSUP.
+ * ldsp_chan_execute writes row k to y + k * ld (ld in samples); it sets *ncols
+ * and, when ld < *ncols, returns LDSP_ERANGE without consuming the input.
+ * Argument errors are decided on the host before any device work.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_chan_s *ldsp_chan_t;
+int ldsp_chan_create(unsigned int M, unsigned int D, unsigned int m, float fc, float as, ldsp_chan_t *q);
+int ldsp_chan_create_taps(unsigned int M, unsigned int D, const float *h, unsigned int L, ldsp_chan_t *q);
+int ldsp_chan_destroy(ldsp_chan_t q);
+int ldsp_chan_reset(ldsp_chan_t q);
+/* Any pointer may be NULL.  skip: input samples before the next call's first output. */
+int ldsp_chan_get_info(ldsp_chan_t q, unsigned int *M, unsigned int *D, unsigned int *L, unsigned int *skip);
+int ldsp_chan_get_taps(ldsp_chan_t q, float *h);                 /* L floats */
+int ldsp_chan_get_scale(ldsp_chan_t q, float *s);
+int ldsp_chan_set_scale(ldsp_chan_t q, float s);
+int ldsp_chan_num_outputs(ldsp_chan_t q, size_t n, size_t *ncols);
+int ldsp_chan_execute(ldsp_chan_t q, const void *x, size_t n, void *y, size_t ld, size_t *ncols, int mem,
+                      void *stream);
+/* Test hook: output frames (columns) per workgroup of the (M, D) kernel. */
+int ldsp_debug_chan_tile(unsigned int M, unsigned int D, size_t *frames);
+
+/* ------------------------------------------------------------------------
+ * Raw IQ conversion. Replaces bytes_to_iq (src/utility.hpp:61-69,
  * wrapper.cpp:13): interleaved native int16 (I, Q) -> complex64 / 32767.
  * nbytes / 4 samples are converted (a trailing partial sample is ignored).
  * ---------------------------------------------------------------------- */

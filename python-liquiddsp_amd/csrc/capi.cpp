@@ -1164,6 +1164,31 @@ struct ldsp_firhilb_s {
     }
 };
 
+// Channelizer (polyphase analysis bank): the prototype, the host-side stream
+// position (samples seen; skip and the output parity follow from it), and on
+// the device the padded taps, the twiddle table and the last P M - 1 input
+// samples, ping-ponged.
+struct ldsp_chan_s {
+    unsigned int M = 0, D = 0, P = 0;
+    std::vector<float> h;
+    float scale = 1.0f;
+    uint64_t seen = 0;                     // input samples since create / reset
+    int device = -1, cur = 0;
+    ldsp::DevBuf dtaps, dtw, hist[2];
+    hipStream_t last = nullptr;
+    ldsp::StreamMark ord;                  // cross-stream call order (ldsp_common.hpp)
+    ldsp::Staging stg;
+    size_t hist_bytes() const { return ((size_t)P * M - 1) * 8; }
+    size_t skip() const { return (size_t)((D - seen % D) % D); }
+    size_t num_outputs(size_t n) const { return n > skip() ? (n - skip() + D - 1) / D : 0; }
+    int parity() const { return (int)(((seen + D - 1) / D) & 1); }   // of the next output's absolute index
+    void zero()
+    {
+        for (auto& b : hist) ldsp::zero_now(b.ensure(hist_bytes(), device), 0, hist_bytes());
+        cur = 0;
+    }
+};
+
 using namespace ldsp;
 
 // Run `fn` translating exceptions into status codes
@@ -3116,6 +3141,179 @@ int ldsp_debug_firhilb_tile(int op, size_t* samples)
         NONNULL(samples);
         LDSP_REQUIRE(op >= LDSP_HILB_R2C && op <= LDSP_HILB_INTERP, "firhilb: unknown op");
         *samples = op == LDSP_HILB_INTERP ? k::kHilbTile / 2 : k::kHilbTile;
+    });
+}
+
+// ---------------------------------------------------------------- Channelizer
+static void chan_check_shape(unsigned int M, unsigned int D)
+{
+    LDSP_REQUIRE(M >= 4 && (M & (M - 1)) == 0, "chan: the channel count must be a power of two, at least 4");
+    LDSP_REQUIRE(D == M || 2 * D == M, "chan: the decimation must be M (critically sampled) or M / 2 (2x oversampled)");
+}
+static ldsp_chan_s* chan_make(unsigned int M, unsigned int D, std::vector<float> h, float scale)
+{
+    if (M > 256) throw Error(LDSP_EUNSUP, "chan: more than 256 channels is not implemented");
+    const size_t P = (h.size() + M - 1) / M;
+    if (P > (size_t)k::kChanMaxP)
+        throw Error(LDSP_EUNSUP, "chan: more than " + std::to_string(k::kChanMaxP) + " taps per branch (L > " +
+                                     std::to_string(k::kChanMaxP) + " M) is not implemented");
+    std::unique_ptr<ldsp_chan_s> o(new ldsp_chan_s());
+    o->M = M;
+    o->D = D;
+    o->P = (unsigned)P;
+    o->h = std::move(h);
+    o->scale = scale;
+    return o.release();
+}
+int ldsp_chan_create(unsigned int M, unsigned int D, unsigned int m, float fc, float as, ldsp_chan_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        chan_check_shape(M, D);
+        LDSP_REQUIRE(m >= 1, "chan: filter semi-length must be at least 1");
+        LDSP_REQUIRE(as > 0.0f, "chan: stop-band attenuation must be > 0");
+        LDSP_REQUIRE(fc < 0.5f, "chan: cutoff must be below 0.5");
+        if (M > 256) throw Error(LDSP_EUNSUP, "chan: more than 256 channels is not implemented");
+        if (2 * (size_t)m + 1 > (size_t)k::kChanMaxP)
+            throw Error(LDSP_EUNSUP, "chan: semi-length above " + std::to_string((k::kChanMaxP - 1) / 2) +
+                                         " is not implemented");
+        if (!(fc > 0.0f)) fc = 0.5f / (float)M;
+        std::vector<float> h = design::firdes_kaiser(2 * M * m + 1, fc, as, 0.0f);
+        double sum = 0.0;
+        for (float v : h) sum += (double)v;
+        *q = chan_make(M, D, std::move(h), (float)(1.0 / sum));
+    });
+}
+int ldsp_chan_create_taps(unsigned int M, unsigned int D, const float* h, unsigned int L, ldsp_chan_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        chan_check_shape(M, D);
+        LDSP_REQUIRE(L >= 1, "chan: at least one tap");
+        NONNULL(h);
+        *q = chan_make(M, D, std::vector<float>(h, h + L), 1.0f);
+    });
+}
+int ldsp_chan_destroy(ldsp_chan_t q)
+{
+    return guard([&] {
+        if (q && q->last) (void)hipStreamSynchronize(q->last);
+        delete q;
+    });
+}
+int ldsp_chan_reset(ldsp_chan_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        q->seen = 0;
+        if (q->device < 0) return;
+        DeviceGuard g(q->device);
+        if (q->last) LDSP_HIP(hipStreamSynchronize(q->last));
+        q->ord.sync();
+        q->zero();
+    });
+}
+int ldsp_chan_get_info(ldsp_chan_t q, unsigned int* M, unsigned int* D, unsigned int* L, unsigned int* skip)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (M) *M = q->M;
+        if (D) *D = q->D;
+        if (L) *L = (unsigned)q->h.size();
+        if (skip) *skip = (unsigned)q->skip();
+    });
+}
+int ldsp_chan_get_taps(ldsp_chan_t q, float* h)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(h);
+        std::copy(q->h.begin(), q->h.end(), h);
+    });
+}
+int ldsp_chan_get_scale(ldsp_chan_t q, float* s) { return guard([&] { NONNULL(q); NONNULL(s); *s = q->scale; }); }
+int ldsp_chan_set_scale(ldsp_chan_t q, float s) { return guard([&] { NONNULL(q); q->scale = s; }); }
+int ldsp_chan_num_outputs(ldsp_chan_t q, size_t n, size_t* ncols)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(ncols);
+        *ncols = q->num_outputs(n);
+    });
+}
+int ldsp_chan_execute(ldsp_chan_t q, const void* x, size_t n, void* y, size_t ld, size_t* ncols, int mem, void* stream)
+{
+    LDSP_RANGE("ldsp_chan_execute");
+    return guard([&] {
+        NONNULL(q);
+        const size_t K = q->num_outputs(n);
+        if (ncols) *ncols = K;
+        if (K > ld) throw Error(LDSP_ERANGE, "chan_execute: row stride below the number of output columns");
+        LDSP_REQUIRE(n == 0 || x, "chan_execute: NULL input");
+        LDSP_REQUIRE(K == 0 || y, "chan_execute: NULL output");
+        LDSP_REQUIRE(mem == LDSP_MEM_HOST || mem == LDSP_MEM_DEVICE, "mem must be LDSP_MEM_HOST or LDSP_MEM_DEVICE");
+        const BufDevice bd(mem, x);
+        const unsigned M = q->M, D = q->D;
+        if (q->device < 0) {
+            const int dev = current_device();
+            DeviceGuard g(dev);
+            std::vector<float> pad(q->h);
+            pad.resize((size_t)k::kChanMaxP * M, 0.0f);
+            upload(q->dtaps, pad, dev);
+            std::vector<float> tw(2 * (size_t)M);             // exp(2 pi i j / M): double, rounded once
+            for (unsigned j = 0; j < M; j++) {
+                const double a = 2.0 * M_PI * (double)j / (double)M;
+                tw[2 * j] = (float)cos(a);
+                tw[2 * j + 1] = (float)sin(a);
+            }
+            upload(q->dtw, tw, dev);
+            q->device = dev;
+            q->zero();
+        }
+        DeviceGuard g(q->device);
+        const Exec e = make_exec(q->device, mem, stream, bd);
+        q->ord.wait(e.stream);
+        // a host-memory call computes into a dense [M][K] device image
+        const size_t dld = e.host ? K : ld;
+        const void* dx = q->stg.dev_in(e, x, n * 8);
+        void* dy = q->stg.dev_out(e, y, (size_t)M * K * 8);
+        if (n > 0) {
+            k::ChanCall c;
+            c.x = dx;
+            c.hist = q->hist[q->cur].p;
+            c.hist_out = q->hist[1 - q->cur].p;
+            c.n = n;
+            c.skip = q->skip();
+            c.ncols = K;
+            c.ld = dld;
+            c.parity = q->parity();
+            c.P = (int)q->P;
+            c.taps = q->dtaps.as<float>();
+            c.tw = q->dtw.p;
+            c.scale = q->scale;
+            c.y = dy;
+            k::chan((int)M, (int)D, c, e.stream);
+            q->cur = 1 - q->cur;
+            q->seen += n;
+        }
+        q->ord.mark(e.stream);
+        q->last = e.stream;
+        if (e.host && ld != K && K > 0) {
+            // rows of the caller's image are ld samples apart
+            LDSP_HIP(hipMemcpy2DAsync(y, ld * 8, dy, K * 8, K * 8, M, hipMemcpyDeviceToHost, e.stream));
+            LDSP_HIP(hipStreamSynchronize(e.stream));
+        } else {
+            q->stg.finish(e, y, (size_t)M * K * 8);
+        }
+    });
+}
+int ldsp_debug_chan_tile(unsigned int M, unsigned int D, size_t* frames)
+{
+    return guard([&] {
+        NONNULL(frames);
+        chan_check_shape(M, D);
+        if (M > 256) throw Error(LDSP_EUNSUP, "chan: more than 256 channels is not implemented");
+        *frames = (size_t)k::chan_frames((int)M);
     });
 }
 

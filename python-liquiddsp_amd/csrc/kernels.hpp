@@ -377,6 +377,28 @@ constexpr int kHilbMaxM = 64;         // semi-length bound (the LDS planes), as 
 constexpr int kHilbTile = 2048;       // input samples per workgroup (INTERP: half as many)
 void hilbert(int op, const void* x, const void* hist, void* hist_out, size_t n, const float* hq, int M, void* y0,
              void* y1, hipStream_t s);
+// k_chan.hip: polyphase analysis filter bank (Channelizer).  M channels (a
+// power of two, 4 .. 256), decimation D = M or M / 2, P = ceil(L / M) <= kChanMaxP
+// taps per branch.  x: n complex64 samples; hist / hist_out: the P M - 1 samples
+// before x[0] / before the next call's x[0], distinct buffers; taps: the
+// prototype zero-padded to kChanMaxP * M floats; tw[j] = exp(2 pi i j / M), j < M.
+// The call's frames are at x[skip + c D], c < ncols = ceil((n - skip) / D) (0 when
+// n <= skip); parity: that of the first frame's absolute index (the D = M / 2
+// sign).  y[k * ld + c] receives channel k.  n = 0 launches nothing.
+constexpr int kChanMaxP = 17;
+constexpr int chan_frames(int M) { return M >= 256 ? 32 : 4096 / M; }   // output frames per workgroup
+struct ChanCall {
+    const void* x;
+    const void* hist;
+    void* hist_out;
+    size_t n, skip, ncols, ld;
+    int parity, P;
+    const float* taps;
+    const void* tw;
+    float scale;
+    void* y;
+};
+void chan(int M, int D, const ChanCall& c, hipStream_t s);
 struct FmState {          // FMStereo mixer loop state (device-resident)
     uint32_t theta, dtheta;
     float pe, alpha, beta;

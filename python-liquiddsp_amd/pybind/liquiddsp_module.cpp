@@ -908,6 +908,107 @@ struct Hilb {
     static size_t twice(size_t n) { return 2 * n; }
 };
 
+// ------------------------------------------------------------------ Channelizer (no reference counterpart)
+// Polyphase analysis bank (ldsp.h): complex64[N] -> complex64[nchan, ncols],
+// row k the channel centred at k / nchan.  The rows of a device result are
+// contiguous views, usable as the channel inputs of execute_many /
+// filter_resample_many.
+struct Channelizer {
+    ldsp_chan_t q = nullptr;
+    unsigned M = 0, D = 0, L = 0;
+    Channelizer(int nchan, const py::object& decim, int m, const py::object& fc, float as, const py::object& taps)
+    {
+        if (nchan < 0) throw py::value_error("Channelizer: nchan must be a power of two, at least 4");
+        const int d = decim.is_none() ? nchan / 2 : decim.cast<int>();
+        if (d < 0) throw py::value_error("Channelizer: decim must be nchan or nchan // 2");
+        if (!taps.is_none()) {
+            std::vector<float> h = to_fvec(taps);
+            check(ldsp_chan_create_taps((unsigned)nchan, (unsigned)d, h.data(), (unsigned)h.size(), &q));
+        } else {
+            if (m < 0) throw py::value_error("Channelizer: m must be >= 1");
+            float f = 0.0f;                                   // the C ABI's default: 0.5 / nchan
+            if (!fc.is_none()) {
+                f = fc.cast<float>();
+                if (!(f > 0.0f && f < 0.5f)) throw py::value_error("Channelizer: Fc must lie in (0, 0.5)");
+            }
+            check(ldsp_chan_create((unsigned)nchan, (unsigned)d, (unsigned)m, f, as, &q));
+        }
+        check(ldsp_chan_get_info(q, &M, &D, &L, nullptr));
+    }
+    Channelizer(const Channelizer&) = delete;
+    ~Channelizer()
+    {
+        if (q) ldsp_chan_destroy(q);
+    }
+    void reset() { check(ldsp_chan_reset(q)); }
+    py::array_t<float> taps()
+    {
+        py::array_t<float> h(L);
+        check(ldsp_chan_get_taps(q, h.mutable_data()));
+        return h;
+    }
+    float get_scale()
+    {
+        float s;
+        check(ldsp_chan_get_scale(q, &s));
+        return s;
+    }
+    void set_scale(float s) { check(ldsp_chan_set_scale(q, s)); }
+    unsigned skip()
+    {
+        unsigned s;
+        check(ldsp_chan_get_info(q, nullptr, nullptr, nullptr, &s));
+        return s;
+    }
+    size_t tile()
+    {
+        size_t f = 0;
+        check(ldsp_debug_chan_tile(M, D, &f));
+        return f;
+    }
+    py::array_t<double> centers()
+    {
+        py::array_t<double> c(M);
+        for (unsigned k = 0; k < M; k++) c.mutable_at(k) = std::fmod((double)k / M + 0.5, 1.0) - 0.5;
+        return c;
+    }
+    size_t num_outputs(size_t n)
+    {
+        size_t c = 0;
+        check(ldsp_chan_num_outputs(q, n, &c));
+        return c;
+    }
+    py::object call(const py::handle& x)
+    {
+        size_t nw = 0;
+        if (is_device_tensor(x)) {
+            DevIn d = dev_in(x, true);
+            const size_t K = num_outputs(d.n);
+            py::object& torch = torch_mod();
+            py::dict kw;
+            kw["dtype"] = torch.attr("complex64");
+            kw["device"] = d.device;
+            py::object out = torch.attr("empty")(py::make_tuple(M, K), **kw);
+            check(ldsp_chan_execute(q, d.ptr, d.n, tptr(out), K, &nw, LDSP_MEM_DEVICE, d.stream));
+            return out;
+        }
+        carr a = carr::ensure(x);
+        if (!a) throw py::error_already_set();
+        const size_t n = (size_t)a.size();
+        const size_t K = num_outputs(n);
+        py::array_t<cf> out({(py::ssize_t)M, (py::ssize_t)K});
+        void* yp = out.mutable_data();
+        const void* xp = a.data();
+        int rc;
+        {
+            py::gil_scoped_release rel;
+            rc = ldsp_chan_execute(q, xp, n, yp, K, &nw, LDSP_MEM_HOST, nullptr);
+        }
+        check(rc);
+        return out;
+    }
+};
+
 // SSBDemod (demod.hpp:155-187): firhilbf_create(25, 60), c2r, one sideband kept
 struct SSBDemod {
     bool usb;
@@ -1473,6 +1574,23 @@ PYBIND11_MODULE(_liquiddsp, m)
         check(ldsp_debug_firhilb_tile(op, &t));
         return t;
     }, "input samples per workgroup of the Hilbert kernel of op (0 r2c, 1 c2r, 2 decim, 3 interp)");
+
+    // ---- Channelizer (beyond the reference: polyphase analysis filter bank)
+    py::class_<Channelizer>(m, "Channelizer")
+        .def(py::init<int, py::object, int, py::object, float, py::object>(), py::arg("nchan"),
+             py::arg("decim") = py::none(), py::arg("m") = 6, py::arg("Fc") = py::none(), py::arg("As") = 60.0f,
+             py::arg("taps") = py::none())
+        .def("reset", &Channelizer::reset)
+        .def("num_outputs", &Channelizer::num_outputs, py::arg("n"),
+             "columns the next call returns for n input samples")
+        .def_property_readonly("nchan", [](Channelizer& c) { return c.M; })
+        .def_property_readonly("decim", [](Channelizer& c) { return c.D; })
+        .def_property_readonly("taps", &Channelizer::taps)
+        .def_property("scale", &Channelizer::get_scale, &Channelizer::set_scale)
+        .def_property_readonly("skip", &Channelizer::skip, "input samples before the next call's first output")
+        .def_property_readonly("tile", &Channelizer::tile, "output columns per workgroup of the kernel")
+        .def_property_readonly("centers", &Channelizer::centers, "channel centres k / nchan wrapped into [-0.5, 0.5)")
+        .def("__call__", &Channelizer::call, "complex64[N] -> complex64[nchan, ncols]");
 
     // ---- FreqDem (wrapper.cpp:183-187), BroadcastAM (wrapper.cpp:259-262)
     py::class_<FreqDem>(m, "FreqDem")
