@@ -242,6 +242,12 @@ int ldsp_debug_iir_path(ldsp_iirfilt_t q, int path);
  * all.  NULL turns it off.  Not thread-safe; for timing studies. */
 int ldsp_debug_iir_sect_trace(void *dev_buf);
 int ldsp_debug_iir_modal_info(ldsp_iirfilt_t q, int *ok, int *modes, int *lookback, double *err);
+/* Test hook, host logic only: the grid of a modal-scan call of n samples --
+ * its 2048-sample units, whether it runs in the one-XCD small-call mode
+ * (units <= 16 x look-back) and the workgroups launched (8 x units in that
+ * mode, else units).  A many-call merges modal launches of equal grid, and only
+ * grids that are a multiple of 8.  Pointers may be NULL. */
+int ldsp_debug_iir_modal_grid(ldsp_iirfilt_t q, size_t n, long *units, int *one_xcd, unsigned int *grid);
 /* Test hook, host logic only (works without a GPU): what a call of n samples
  * runs with the current mode and forced path.  path: 0 speculative exact chunks,
  * 1 sequential exact, 2 modal scan, 3 blocked scan (D <= 8), 4 chunked scan.
@@ -307,6 +313,16 @@ int ldsp_debug_agc_tsa_reruns(ldsp_agc_t q, unsigned int *count);
 int ldsp_debug_agc_perturb(ldsp_agc_t q, int on);
 int ldsp_debug_agc_rounds(ldsp_agc_t q, int rounds);
 int ldsp_debug_agc_reruns(ldsp_agc_t q, unsigned int *runfix, unsigned int *verify);
+/* Test hook, host logic only (works without a GPU): the path the next call of n
+ * samples takes, from the function ldsp_agc_execute itself decides with --
+ * *path 0 the sequential loop, 1 small-call chunks from the true state, 2
+ * chunk-parallel; the warm-up lengths W (exact) and Wa (approximate) of the
+ * current bandwidth; the chunk length C (0 on path 0); the input history a
+ * speculative call needs (W + Wa + 256) and how much of it the object holds;
+ * *spec 1 when the call runs from the history alone (front, repair, verify
+ * launches instead of front, back).  Pointers may be NULL. */
+int ldsp_debug_agc_dispatch(ldsp_agc_t q, size_t n, int *path, int *W, int *Wa, int *C, long *hist_len,
+                            long *hist_valid, int *spec);
 int ldsp_agc_destroy(ldsp_agc_t q);
 int ldsp_agc_reset(ldsp_agc_t q);
 int ldsp_agc_set_bandwidth(ldsp_agc_t q, float bw);
@@ -391,6 +407,12 @@ int ldsp_debug_walk_fold(uint32_t u, int32_t b, int left_gap, int right_gap, uin
  * A timed-out walk raises LDSP_EHIP at the object's next call or state read
  * until ldsp_ampmodem_reset.  Synchronises. */
 int ldsp_debug_ampmodem_handoff(ldsp_ampmodem_t q, uint64_t wait_ticks, int epoch_skew);
+/* Test hook, host logic only (works without a GPU): *parallel 1 when a call of
+ * n samples runs the chunk-parallel PLL (scan, candidates, walk), 0 for the
+ * sequential loop (the threshold differs between carrier and Costas modems);
+ * *batchable 1 when a many-call merges this object's launches (dsb), 0 when it
+ * makes the whole many-call run object by object.  Pointers may be NULL. */
+int ldsp_debug_ampmodem_dispatch(ldsp_ampmodem_t q, size_t n, int *parallel, int *batchable);
 /* Diagnostics, no reference counterpart: the walker's early hand-off for the
  * calls that follow (1 on, the default; 0 off: every walker waits for the
  * previous walk in stream order, so a kernel trace's k_pll_walk duration is the

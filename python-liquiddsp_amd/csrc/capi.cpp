@@ -780,6 +780,14 @@ struct IirObj {
         p.bstart = (double*)bsc3.ensure((size_t)nblk * ncomp() * D * sizeof(double), device);
         return p;
     }
+    // one XCD while its 32 CUs stream the call faster than a range start
+    // recomputes its J predecessors (~2.5 us each): up to 16 J units
+    // (modal_plan, ldsp_debug_iir_modal_grid)
+    int modal_one_xcd(size_t n) const
+    {
+        static const int onex = LDSP_KNOB("LDSP_IIR_ONEXCD", -1);
+        return onex >= 0 ? onex : (k::iir_modal_units(n) <= 16L * mf.J ? 1 : 0);
+    }
     // Modal scan plan: the tables (uploaded with the state), the per-unit
     // granules (zero when allocated: below every epoch) and this call's epoch.
     k::IirModalPlan modal_plan(size_t n)
@@ -803,10 +811,7 @@ struct IirObj {
         p.agg = magg.as<uint64_t>();
         p.epoch = m_epoch;
         p.recompute = path_force == 3 ? 1 : 0;
-        // one XCD while its 32 CUs stream the call faster than a range start
-        // recomputes its J predecessors (~2.5 us each): up to 16 J units
-        static const int onex = LDSP_KNOB("LDSP_IIR_ONEXCD", -1);
-        p.one_xcd = onex >= 0 ? onex : (units <= 16L * mf.J ? 1 : 0);
+        p.one_xcd = modal_one_xcd(n);
         p.variant = LDSP_KNOB("LDSP_IIR_VARIANT", 0);
         return p;
     }
@@ -1958,6 +1963,17 @@ int ldsp_debug_iir_modal_info(ldsp_iirfilt_t q, int* ok, int* modes, int* lookba
         if (err) *err = q->mf.err;
     });
 }
+int ldsp_debug_iir_modal_grid(ldsp_iirfilt_t q, size_t n, long* units, int* one_xcd, unsigned int* grid)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(q->mf.ok, "iirfilt: this filter has no valid modal form");
+        const int onex = q->modal_one_xcd(n);
+        if (units) *units = k::iir_modal_units(n);
+        if (one_xcd) *one_xcd = onex;
+        if (grid) *grid = k::iir_modal_grid(n, onex);
+    });
+}
 int ldsp_debug_iir_dispatch(ldsp_iirfilt_t q, size_t n, int* path, int* sect_tile, int* size_class, int* spec_W,
                             int* spec_staged)
 {
@@ -2324,6 +2340,70 @@ int ldsp_agc_set_mode(ldsp_agc_t q, int mode)
     });
 }
 
+// The path of a call of n samples (ldsp_agc_execute, ldsp_debug_agc_dispatch):
+// host logic only, nothing of the object changes.
+struct AgcChoice {
+    enum Path { kSeq = 0, kTsa = 1, kPar = 2 };
+    int path = kSeq;                  // sequential loop, small-call chunks from the true state, chunk-parallel
+    int W = 0, Wa = 0;                // exact and approximate warm-up lengths of this bandwidth
+    int C = 0;                        // chunk length (0: sequential)
+    long nchunks = 0;
+    long hist_len = 0;                // input history a speculative call needs: W + Wa + kAgcPow
+    bool spec = false;                // chunk-parallel from the history alone (front, repair, verify)
+};
+static AgcChoice agc_choice(const AgcObj* q, size_t n)
+{
+    AgcChoice ch;
+    // exact warm-up W = 5/bandwidth after an approximate one of Wa = 40/bandwidth
+    // (k_agc.hip); measured on the AM chain at bandwidth 0.01 the exact loop then
+    // coalesces within ~110 samples on average, 2834 at worst.  The chunks that
+    // have not by then (~70 of 1 573 per 64 Mi call at W = 5/bw, 7 at 20/bw) go
+    // to the windowed one-wave run-fix, which stops at the first checkpoint that
+    // meets the stored trajectory: single call 3.72 -> 3.42 ms against W = 20/bw
+    // (W = 3/bw: 3.71, more runs), 20-step and batched channels unchanged.
+    const float a = q->h.alpha > 1e-6f ? q->h.alpha : 1e-6f;
+    static const float wmul = LDSP_KNOB_F("LDSP_AGC_WMUL", 5.0f);
+    static const float wamul = LDSP_KNOB_F("LDSP_AGC_WAMUL", 40.0f);
+    static const bool nospec = LDSP_KNOB("LDSP_AGC_NOSPEC", 0) != 0;   // A/B: every call from the true state
+    const int W = (int)std::min(1 << 18, std::max(256, (int)(wmul / a)));
+    const int Wa = (int)std::min(1 << 20, std::max(1024, (int)(wamul / a)));
+    ch.W = W;
+    ch.Wa = Wa;
+    ch.hist_len = (long)W + Wa + k::kAgcPow;
+    // Latency per step on one lane (scripts/ubench/loop_lat.hip): approximate
+    // 0.06 us, exact 0.25 us.  Chunk-parallel from guesses (every chunk Wa
+    // approximate + W + 256 exact steps, ~0.8 us at bandwidth 0.01, overlapping
+    // the previous call) once a call is long enough that the true-start chunks
+    // below would take more than half of that.
+    static const size_t parmin = (size_t)LDSP_KNOB("LDSP_AGC_PARMIN", 0L);
+    const bool par = n >= (parmin ? parmin : std::max<size_t>(2048, (size_t)(0.5 * (0.06 * Wa + 0.25 * (W + 256)) / 0.06)));
+    // below that, from ~300 samples: chunks approximating from the true state
+    // (latency 0.06 us per sample before the last chunk + 256 exact steps)
+    static const size_t tsamin = (size_t)LDSP_KNOB("LDSP_AGC_TSAMIN", 320L);
+    const bool tsa = !par && n >= tsamin;
+    ch.path = par ? AgcChoice::kPar : tsa ? AgcChoice::kTsa : AgcChoice::kSeq;
+    // a changed bandwidth (another hist_len) restarts the history
+    const long valid = ch.hist_len == q->hist_len ? q->hist_valid : 0;
+    ch.spec = !nospec && !tsa && valid >= ch.hist_len;
+    if (n > 0 && (par || tsa)) {
+        // chunk length: every chunk re-runs Wa + W warm-up steps (6 000 at
+        // bandwidth 0.01) for its C outputs, so C = 1024 does a quarter of the
+        // front's work of C = 256 at ~20 % more latency (hidden under the PLL
+        // walk in a streamed chain); measured on 8 channels per GPU 6.6 -> 6.3
+        // ms per step (scripts/agc_chunk_sweep.sh).  Small calls (tsa): the
+        // one wave runs the approximate loop up to the last chunk's start and
+        // then C exact steps, so the shortest chunks that still fit 64 lanes
+        // (C >= 32) cut the exact tail: a README call (1 573 samples) 256 -> 32
+        // exact steps after the same approximate run.  Multi-wave tsa calls keep 256.
+        static const int agc_c = LDSP_KNOB("LDSP_AGC_C", 1024);
+        static const int tsa_cmin = LDSP_KNOB("LDSP_AGC_TSA_CMIN", 32);
+        const int c64 = (int)(((n + 63) / 64 + 31) / 32 * 32);      // 64 chunks of a multiple of 32
+        ch.C = tsa ? (c64 <= 256 ? std::max(tsa_cmin, c64) : 256) : agc_c;
+        ch.nchunks = (long)((n + ch.C - 1) / ch.C);
+    }
+    return ch;
+}
+
 // Two halves per call (k_agc.hip): the front runs the speculative chunks --
 // from the input history alone once it holds hist_len samples, so call k + 1's
 // front overlaps call k's back half on another stream -- and the back half
@@ -2358,56 +2438,29 @@ int ldsp_agc_execute(ldsp_agc_t q, const void* x, size_t n, void* y, uint8_t* st
         // meets the stored trajectory: single call 3.72 -> 3.42 ms against W = 20/bw
         // (W = 3/bw: 3.71, more runs), 20-step and batched channels unchanged
         // (gpurun_out r05zo).
-        const float a = q->h.alpha > 1e-6f ? q->h.alpha : 1e-6f;
-        static const float wmul = LDSP_KNOB_F("LDSP_AGC_WMUL", 5.0f);
-        static const float wamul = LDSP_KNOB_F("LDSP_AGC_WAMUL", 40.0f);
         // repair rounds (flag + run-by-run re-run launches) before the one-wave
         // verifier, which re-runs whatever a round left: on the bench chain every
         // repair lands in round 1 (rounds 2-3 found nothing), and with 8 channels
         // per GPU each launch on a chain waits 0.1-0.2 ms for a slot, so one round
         // (8 channels 5.62-5.78 vs 5.83-6.24 ms per step, profiles/r04v_channels.txt)
         static const int rounds = LDSP_KNOB("LDSP_AGC_ROUNDS", 1);
-        static const bool nospec = LDSP_KNOB("LDSP_AGC_NOSPEC", 0) != 0;   // A/B: every call from the true state
-        const int W = (int)std::min(1 << 18, std::max(256, (int)(wmul / a)));
-        const int Wa = (int)std::min(1 << 20, std::max(1024, (int)(wamul / a)));
-        const long hl = (long)W + Wa + k::kAgcPow;
+        const AgcChoice ch = agc_choice(q, n);
+        const int W = ch.W, Wa = ch.Wa;
+        const long hl = ch.hist_len;
         if (hl != q->hist_len) {             // bandwidth changed: history restarts
             q->hist_len = hl;
             q->hist_valid = 0;
             for (int i = 0; i < 3; i++) q->hist[i].ensure((size_t)hl * 8, q->device);
         }
-        // Latency per step on one lane (scripts/ubench/loop_lat.hip): approximate
-        // 0.06 us, exact 0.25 us.  Chunk-parallel from guesses (every chunk Wa
-        // approximate + W + 256 exact steps, ~0.8 us at bandwidth 0.01, overlapping
-        // the previous call) once a call is long enough that the true-start chunks
-        // below would take more than half of that.
-        static const size_t parmin = (size_t)LDSP_KNOB("LDSP_AGC_PARMIN", 0L);
-        const bool par = n >= (parmin ? parmin : std::max<size_t>(2048, (size_t)(0.5 * (0.06 * Wa + 0.25 * (W + 256)) / 0.06)));
-        // below that, from ~300 samples: chunks approximating from the true state
-        // (latency 0.06 us per sample before the last chunk + 256 exact steps)
-        static const size_t tsamin = (size_t)LDSP_KNOB("LDSP_AGC_TSAMIN", 320L);
-        const bool tsa = !par && n >= tsamin;
-        const bool spec = !nospec && !tsa && q->hist_valid >= hl;
+        const bool par = ch.path == AgcChoice::kPar, tsa = ch.path == AgcChoice::kTsa, spec = ch.spec;
         k::SpecPlan p;
         if (n > 0 && (par || tsa)) {
             p.W = tsa ? 0 : W;                 // tsa: every chunk from 1 on is checked against its predecessor
             p.Wa = Wa;
             p.rounds = tsa ? 1 : std::max(0, std::min(q->rounds_force >= 0 ? q->rounds_force : rounds, 6));
             // (tsa: one run covers the rare deviation)
-            // chunk length: every chunk re-runs Wa + W warm-up steps (6 000 at
-            // bandwidth 0.01) for its C outputs, so C = 1024 does a quarter of the
-            // front's work of C = 256 at ~20 % more latency (hidden under the PLL
-            // walk in a streamed chain); measured on 8 channels per GPU 6.6 -> 6.3
-            // ms per step (scripts/agc_chunk_sweep.sh).  Small calls (tsa): the
-            // one wave runs the approximate loop up to the last chunk's start and
-            // then C exact steps, so the shortest chunks that still fit 64 lanes
-            // (C >= 32) cut the exact tail: a README call (1 573 samples) 256 -> 32
-            // exact steps after the same approximate run.  Multi-wave tsa calls keep 256.
-            static const int agc_c = LDSP_KNOB("LDSP_AGC_C", 1024);
-            static const int tsa_cmin = LDSP_KNOB("LDSP_AGC_TSA_CMIN", 32);
-            const int c64 = (int)(((n + 63) / 64 + 31) / 32 * 32);      // 64 chunks of a multiple of 32
-            p.C = tsa ? (c64 <= 256 ? std::max(tsa_cmin, c64) : 256) : agc_c;
-            p.nchunks = (long)((n + p.C - 1) / p.C);
+            p.C = ch.C;
+            p.nchunks = ch.nchunks;
             p.scratch = q->scr[sl].ensure(k::agc_scratch_bytes(p.nchunks, p.C), q->device);
             p.hist = q->hist[h3].p;
             p.H = spec ? (int)hl : 0;
@@ -3450,6 +3503,30 @@ int ldsp_fmstereo_execute(ldsp_fmstereo_t q, const void* x, size_t n, void* y, s
         q->ord.mark(e.stream);
         q->last = e.stream;
         q->stg.finish(e, y, 2 * k * 4);
+    });
+}
+
+int ldsp_debug_agc_dispatch(ldsp_agc_t q, size_t n, int* path, int* W, int* Wa, int* C, long* hist_len,
+                            long* hist_valid, int* spec)
+{
+    return guard([&] {
+        NONNULL(q);
+        const AgcChoice ch = agc_choice(q, n);
+        if (path) *path = ch.path;
+        if (W) *W = ch.W;
+        if (Wa) *Wa = ch.Wa;
+        if (C) *C = ch.C;
+        if (hist_len) *hist_len = ch.hist_len;
+        if (hist_valid) *hist_valid = ch.hist_len == q->hist_len ? q->hist_valid : 0;
+        if (spec) *spec = ch.spec ? 1 : 0;
+    });
+}
+int ldsp_debug_ampmodem_dispatch(ldsp_ampmodem_t q, size_t n, int* parallel, int* batchable)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (parallel) *parallel = k::pll_parallel(n, q->suppressed ? 1 : 0) ? 1 : 0;
+        if (batchable) *batchable = q->type == 0 ? 1 : 0;
     });
 }
 

@@ -642,7 +642,7 @@ void launch_modal(const IirModalCoef& cf, const void* x, size_t n, const double*
     // blocks b = q mod 8 share an XCD (the kernel's unit ranges): a merged launch
     // keeps that only when every object's grid is a multiple of 8 (batch.hpp)
     const IirModalArgs a{cf, x, (long)n, nw, p, st_in, st_out, y, f};
-    const dim3 g((unsigned)(p.one_xcd ? 8 * nw : nw)), b(64 * NC);
+    const dim3 g(iir_modal_grid(n, p.one_xcd)), b(64 * NC);
     if constexpr (IQ16)
         launch<IirModalArgs>(RS ? "k_iir_modal_rs" : "k_iir_modal", k_iir_modal<NC, M, IQ16, RS>, nullptr, g, b, 0, s, a,
                              true);
@@ -654,6 +654,12 @@ void launch_modal(const IirModalCoef& cf, const void* x, size_t n, const double*
 } // namespace
 
 long iir_modal_units(size_t n) { return (long)((n + kUnit - 1) / kUnit); }
+
+unsigned iir_modal_grid(size_t n, int one_xcd)
+{
+    const long nw = iir_modal_units(n);
+    return (unsigned)(one_xcd ? 8 * nw : nw);
+}
 
 size_t iir_resamp_side_bytes(size_t n, int sub_len, bool cplx)
 {

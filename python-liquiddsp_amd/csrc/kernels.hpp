@@ -187,6 +187,7 @@ void iir_modal_resamp(bool cplx, const IirModalCoef& cf, const void* x, size_t n
                       double* st_out, const IirModalPlan& p, const IirResampFuse& f, const void* hist,
                       void* hist_out, hipStream_t s);
 long iir_modal_units(size_t n);   // workgroups (2048-sample look-back units) of a call
+unsigned iir_modal_grid(size_t n, int one_xcd);   // workgroups launched: 8 x units in the one-XCD mode (7 of 8 return at once)
 void iir_modal(bool cplx, const IirModalCoef& cf, const void* x, size_t n, const double* st_in, double* st_out,
                const IirModalPlan& p, void* y, hipStream_t s, bool iq16 = false);
 // Speculative exact evaluation for fast-decaying filters: chunks start from a

@@ -1182,6 +1182,15 @@ void bind_iir_common(P& c)
             check(ldsp_debug_iir_modal_info(c.q, &ok, &m, &j, &err));
             return py::make_tuple(ok != 0, m, j, err);
         })
+        .def("_modal_grid", [](C& c, size_t n) {
+            long units = 0;
+            int onex = 0;
+            unsigned grid = 0;
+            check(ldsp_debug_iir_modal_grid(c.q, n, &units, &onex, &grid));
+            return py::make_tuple(units, onex != 0, grid);
+        }, py::arg("n"),
+             "test hook (host logic only): (units, one-XCD mode, workgroups) of a modal-scan call of n samples "
+             "(ldsp_debug_iir_modal_grid)")
         .def("_dispatch", &iir_dispatch<C>, py::arg("n"), kIirDispatchDoc);
 }
 
@@ -1231,6 +1240,15 @@ void bind_proto(py::module_& m, const char* name)
             check(ldsp_debug_iir_modal_info(c.q, &ok, &m, &j, &err));
             return py::make_tuple(ok != 0, m, j, err);
         })
+        .def("_modal_grid", [](C& c, size_t n) {
+            long units = 0;
+            int onex = 0;
+            unsigned grid = 0;
+            check(ldsp_debug_iir_modal_grid(c.q, n, &units, &onex, &grid));
+            return py::make_tuple(units, onex != 0, grid);
+        }, py::arg("n"),
+             "test hook (host logic only): (units, one-XCD mode, workgroups) of a modal-scan call of n samples "
+             "(ldsp_debug_iir_modal_grid)")
         .def("_dispatch", &iir_dispatch<C>, py::arg("n"), kIirDispatchDoc);
 }
 
@@ -1338,6 +1356,7 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def(py::init<float>(), py::arg("sample_rate") = 48000)
         .def("freqresponse", &DeemphasisFilter::freqresponse)
         .def("__call__", &DeemphasisFilter::call)
+        .def("_dispatch", &iir_dispatch<DeemphasisFilter>, py::arg("n"), kIirDispatchDoc)
         .def("reset", &DeemphasisFilter::reset);
 
     // ---- AmpModem (wrapper.cpp:189-199)
@@ -1360,6 +1379,13 @@ PYBIND11_MODULE(_liquiddsp, m)
              }, py::arg("wait_ticks"), py::arg("epoch_skew"),
              "test hook: the early walker's wait bound (10 ns ticks, 0 = 1 s) and a skew of the epoch it waits for "
              "(ldsp_debug_ampmodem_handoff)")
+        .def("_dispatch", [](AmpModem& a, size_t n) {
+                 int par = 0, bat = 0;
+                 check(ldsp_debug_ampmodem_dispatch(a.q, n, &par, &bat));
+                 return py::make_tuple(par ? "par" : "seq", bat != 0);
+             }, py::arg("n"),
+             "test hook (host logic only): ('par' | 'seq', batchable) of a call of n samples "
+             "(ldsp_debug_ampmodem_dispatch)")
         .def("__call__", &AmpModem::demod);
 
     // ---- NCO (wrapper.cpp:201-212)
@@ -1662,6 +1688,15 @@ PYBIND11_MODULE(_liquiddsp, m)
             check(ldsp_debug_agc_reruns(a.q, &rf, &vf));
             return py::make_tuple(rf, vf);
         }, "test hook: (repair-round, verifier) chunk re-runs since creation (ldsp_debug_agc_reruns)")
+        .def("_dispatch", [](AGC& a, size_t n) {
+            static const char* const names[] = {"seq", "small", "par"};
+            int path = 0, W = 0, Wa = 0, C = 0, spec = 0;
+            long hl = 0, hv = 0;
+            check(ldsp_debug_agc_dispatch(a.q, n, &path, &W, &Wa, &C, &hl, &hv, &spec));
+            return py::make_tuple(names[path], W, Wa, C, hl, hv, spec != 0);
+        }, py::arg("n"),
+             "test hook (host logic only): (path, W, Wa, C, hist_len, hist_valid, speculative) of the next call of n "
+             "samples; path is 'seq', 'small' or 'par' (ldsp_debug_agc_dispatch)")
         .def("_tsa_reruns", [](AGC& a) {
             unsigned c = 0;
             check(ldsp_debug_agc_tsa_reruns(a.q, &c));

@@ -49,6 +49,14 @@ static void iir_designs(void)
                         int ok = 0, modes = 0, lb = 0;
                         double err = 0;
                         CHECK(ldsp_debug_iir_modal_info(q, &ok, &modes, &lb, &err) == LDSP_OK);
+                        if (ok) {
+                            long units = 0;
+                            int onex = -1;
+                            unsigned int grid = 0;
+                            CHECK(ldsp_debug_iir_modal_grid(q, 300007, &units, &onex, &grid) == LDSP_OK);
+                            CHECK(units == 147 && grid == (onex ? 8u * 147u : 147u));
+                            CHECK(ldsp_debug_iir_modal_grid(q, 0, NULL, NULL, NULL) == LDSP_OK);
+                        }
                         CHECK(ldsp_iirfilt_set_mode(q, LDSP_MODE_EXACT) == LDSP_OK);
                         CHECK(ldsp_iirfilt_reset(q) == LDSP_OK);
                         CHECK(ldsp_iirfilt_destroy(q) == LDSP_OK);
@@ -164,6 +172,14 @@ static void loops(void)
     float v;
     CHECK(ldsp_agc_set_bandwidth(g, 0.02f) == LDSP_OK && ldsp_agc_get_bandwidth(g, &v) == LDSP_OK);
     CHECK(ldsp_agc_lock(g, 1) == LDSP_OK && ldsp_agc_lock(g, 0) == LDSP_OK);
+    {
+        int path = -1, W = 0, Wa = 0, Cc = -1, spec = -1;
+        long hl = 0, hv = -1;
+        CHECK(ldsp_debug_agc_dispatch(g, 40000, &path, &W, &Wa, &Cc, &hl, &hv, &spec) == LDSP_OK);
+        CHECK(path == 2 && W == 256 && Wa >= 1024 && Cc == 1024 && hl == W + Wa + 256 && hv == 0 && spec == 0);
+        CHECK(ldsp_debug_agc_dispatch(g, 0, &path, NULL, NULL, &Cc, NULL, NULL, NULL) == LDSP_OK && path == 0 && Cc == 0);
+        CHECK(ldsp_debug_agc_dispatch(NULL, 1, &path, NULL, NULL, NULL, NULL, NULL, NULL) != LDSP_OK);
+    }
     CHECK(ldsp_agc_squelch_enable(g, 1) == LDSP_OK && ldsp_agc_squelch_set_threshold(g, -30.0f) == LDSP_OK);
     CHECK(ldsp_agc_squelch_get_threshold(g, &v) == LDSP_OK && ldsp_agc_squelch_set_timeout(g, 7) == LDSP_OK);
     int st = 0;
@@ -186,6 +202,10 @@ static void loops(void)
             CHECK(ldsp_ampmodem_get_taps(q, lp, dc, hq) == LDSP_OK);
             uint32_t t1, t2;
             CHECK(ldsp_ampmodem_get_pll_state(q, &t1, &t2) == LDSP_OK);
+            int par = -1, bat = -1;
+            CHECK(ldsp_debug_ampmodem_dispatch(q, 1100, &par, &bat) == LDSP_OK);
+            CHECK(par == (sup ? 0 : 1) && bat == (type == 0 ? 1 : 0));
+            CHECK(ldsp_debug_ampmodem_dispatch(q, 0, NULL, NULL) == LDSP_OK);
             CHECK(ldsp_ampmodem_demodulate(q, xx, 16, y, LDSP_MEM_HOST, NULL) == LDSP_EHIP);
             CHECK(ldsp_ampmodem_reset(q) == LDSP_OK && ldsp_ampmodem_destroy(q) == LDSP_OK);
         }
