@@ -551,6 +551,66 @@ int ldsp_chan_execute(ldsp_chan_t q, const void *x, size_t n, void *y, size_t ld
 int ldsp_debug_chan_tile(unsigned int M, unsigned int D, size_t *frames);
 
 /* ------------------------------------------------------------------------
+ * Spectrogram: a streaming Welch periodogram, one complex64 stream to rows of
+ * power per bin and a running mean of them.  No reference counterpart
+ * (liquid's spgramcf / spwaterfallcf are the same block: a zeroed window
+ * buffer and a transform every `delay` pushes); the definition is this
+ * library's own.  The stream x[t] counts t from 0 since creation or reset,
+ * with zeros before t = 0; N = nfft, a window w of W taps (1 <= W <= N), a hop
+ * d (1 <= d <= W) and A >= 1 transforms per row.  Transform s = 0, 1, .. is
+ * taken when sample t = (s + 1) d - 1 arrives:
+ *   X_s[k] = sum_{i<W} w[i] x[(s + 1) d - W + i] exp(-2 pi i k i / N)    k < N
+ *   P_s[k] = re(X_s[k])^2 + im(X_s[k])^2
+ *   row r  = (1 / A) sum_{s = rA}^{rA + A - 1} P_s
+ *   psd    = (1 / S) sum P_s over the S transforms since create / reset / clear
+ * The windowed samples are FFT inputs 0 .. W - 1, zero-padded to N.  Bins are
+ * in FFT order: bin k is at k / N cycles per sample, k >= N / 2 the negative
+ * frequencies.  With T samples seen before a call of n samples the call takes
+ * floor((T + n) / d) - floor(T / d) transforms and returns the rows whose last
+ * transform it delivers: floor(s1 / A) - floor(s0 / A) with s0, s1 the
+ * transform counts since create / reset before and after (clear does not move
+ * the row schedule).  Calls of any length, 0 included, are allowed, and a
+ * row's bits do not depend on how the stream is cut into calls.
+ * Named windows (t = i / (W - 1); W = 1 gives w = [1]) are computed in double,
+ * normalised in double to unit noise gain, sum w[i]^2 = 1 (white noise of
+ * variance v reads v in every bin), and rounded once to float32:
+ *   RECT 1;  HANN 0.5 - 0.5 cos 2 pi t;  HAMMING 0.53836 - 0.46164 cos 2 pi t;
+ *   BLACKMANHARRIS 0.35875 - 0.48829 cos 2 pi t + 0.14128 cos 4 pi t
+ *                  - 0.01168 cos 6 pi t
+ * ldsp_spgram_create_window takes w as given (not normalised).
+ *   N not a power of two, W = 0, W > N, d = 0, A = 0, an unknown wtype:
+ *   LDSP_EINVAL;  a power-of-two N below 256 or above 4096, d > W: LDSP_EUNSUP.
+ * ldsp_spgram_execute writes row r to y + r * ld (ld in floats, >= nfft, else
+ * LDSP_EINVAL); y = NULL accumulates only (ld is ignored, *nrows still set).
+ * ldsp_spgram_get_psd copies the mean to a host array of nfft doubles (zeros
+ * while S = 0) and synchronises.  ldsp_spgram_clear zeroes the accumulator and
+ * S only; ldsp_spgram_reset also the history, T and the unfinished row.  The
+ * accumulator is float64 on the device and is added to in a fixed order: the
+ * same sequence of calls gives the same bits, with or without row stores.
+ * Argument errors are decided on the host before any device work.
+ * Not built: exponential averaging, real input, d > W, dB output, fftshift.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_spgram_s *ldsp_spgram_t;
+enum { LDSP_WIN_RECT = 0, LDSP_WIN_HANN = 1, LDSP_WIN_HAMMING = 2, LDSP_WIN_BLACKMANHARRIS = 3 };
+int ldsp_spgram_create(unsigned int nfft, int wtype, unsigned int W, unsigned int d, unsigned int A,
+                       ldsp_spgram_t *q);
+int ldsp_spgram_create_window(unsigned int nfft, const float *w, unsigned int W, unsigned int d, unsigned int A,
+                              ldsp_spgram_t *q);
+int ldsp_spgram_destroy(ldsp_spgram_t q);
+int ldsp_spgram_reset(ldsp_spgram_t q);
+int ldsp_spgram_clear(ldsp_spgram_t q);
+/* Any output pointer may be NULL.  samples: T; transforms: S. */
+int ldsp_spgram_get_info(ldsp_spgram_t q, unsigned int *nfft, unsigned int *W, unsigned int *d, unsigned int *A,
+                         uint64_t *samples, uint64_t *transforms);
+int ldsp_spgram_get_window(ldsp_spgram_t q, float *w);           /* W floats */
+int ldsp_spgram_num_outputs(ldsp_spgram_t q, size_t n, size_t *ntransforms, size_t *nrows);
+int ldsp_spgram_execute(ldsp_spgram_t q, const void *x, size_t n, float *y, size_t ld, size_t *nrows, int mem,
+                        void *stream);
+int ldsp_spgram_get_psd(ldsp_spgram_t q, double *psd, uint64_t *transforms);
+/* Test hook: transforms per workgroup of the nfft kernel (at A > 1: whole rows, at least one). */
+int ldsp_debug_spgram_tile(unsigned int nfft, size_t *transforms);
+
+/* ------------------------------------------------------------------------
  * Raw IQ conversion. Replaces bytes_to_iq (src/utility.hpp:61-69,
  * wrapper.cpp:13): interleaved native int16 (I, Q) -> complex64 / 32767.
  * nbytes / 4 samples are converted (a trailing partial sample is ignored).

@@ -1194,6 +1194,36 @@ struct ldsp_chan_s {
     }
 };
 
+// Spectrogram (streaming Welch periodogram): the window, the host-side counts
+// (samples since reset, transforms since clear; the schedule follows from
+// them), and on the device the padded window, the twiddle table, the last
+// W - 1 input samples and the unfinished row's sum (both ping-ponged), the
+// float64 accumulator and the per-workgroup sums it is fed from.
+struct ldsp_spgram_s {
+    unsigned int N = 0, W = 0, d = 0, A = 0;
+    std::vector<float> w;
+    uint64_t seen = 0;                     // input samples since create / reset
+    uint64_t nacc = 0;                     // transforms since create / reset / clear
+    int device = -1, cur = 0, ccur = 0, rcur = 0;
+    // carry: the unfinished row's sum (blocked averages: the unfinished block's);
+    // blk, rcarry: a blocked average's block sums and its unfinished row's
+    ldsp::DevBuf dwin, dtw, hist[2], carry[2], rcarry[2], dpsd, part, blk;
+    hipStream_t last = nullptr;
+    ldsp::StreamMark ord;
+    ldsp::Staging stg;
+    size_t hist_bytes() const { return std::max<size_t>((size_t)W - 1, 1) * 8; }
+    size_t transforms(size_t n) const { return (size_t)((seen + n) / d - seen / d); }
+    size_t rows(size_t n) const { return (size_t)((seen + n) / d / A - seen / d / A); }
+    void zero_stream()
+    {
+        for (auto& b : hist) ldsp::zero_now(b.ensure(hist_bytes(), device), 0, hist_bytes());
+        for (auto& b : carry) ldsp::zero_now(b.ensure((size_t)N * 4, device), 0, (size_t)N * 4);
+        for (auto& b : rcarry) ldsp::zero_now(b.ensure((size_t)N * 4, device), 0, (size_t)N * 4);
+        cur = ccur = rcur = 0;
+    }
+    void zero_psd() { ldsp::zero_now(dpsd.ensure((size_t)N * 8, device), 0, (size_t)N * 8); }
+};
+
 using namespace ldsp;
 
 // Run `fn` translating exceptions into status codes
@@ -3367,6 +3397,261 @@ int ldsp_debug_chan_tile(unsigned int M, unsigned int D, size_t* frames)
         chan_check_shape(M, D);
         if (M > 256) throw Error(LDSP_EUNSUP, "chan: more than 256 channels is not implemented");
         *frames = (size_t)k::chan_frames((int)M);
+    });
+}
+
+// ---------------------------------------------------------------- Spectrogram
+static void spgram_check_shape(unsigned int N, unsigned int W, unsigned int d, unsigned int A)
+{
+    LDSP_REQUIRE(N >= 1 && (N & (N - 1)) == 0, "spgram: nfft must be a power of two");
+    if (N < 256 || N > 4096) throw Error(LDSP_EUNSUP, "spgram: nfft below 256 or above 4096 is not implemented");
+    LDSP_REQUIRE(W >= 1 && W <= N, "spgram: the window length must lie in 1 .. nfft");
+    LDSP_REQUIRE(d >= 1, "spgram: the delay must be at least 1");
+    if (d > W) throw Error(LDSP_EUNSUP, "spgram: a delay above the window length is not implemented");
+    LDSP_REQUIRE(A >= 1, "spgram: average must be at least 1");
+}
+static ldsp_spgram_s* spgram_make(unsigned int N, unsigned int W, unsigned int d, unsigned int A, std::vector<float> w)
+{
+    std::unique_ptr<ldsp_spgram_s> o(new ldsp_spgram_s());
+    o->N = N;
+    o->W = W;
+    o->d = d;
+    o->A = A;
+    o->w = std::move(w);
+    return o.release();
+}
+// the named windows: double, normalised to sum w^2 = 1 in double, rounded once
+static std::vector<float> spgram_window(int wtype, unsigned int W)
+{
+    std::vector<double> v(W);
+    for (unsigned i = 0; i < W; i++) {
+        const double t = W > 1 ? (double)i / (double)(W - 1) : 0.0;
+        const double c1 = cos(2.0 * M_PI * t), c2 = cos(4.0 * M_PI * t), c3 = cos(6.0 * M_PI * t);
+        switch (wtype) {
+        case LDSP_WIN_RECT: v[i] = 1.0; break;
+        case LDSP_WIN_HANN: v[i] = 0.5 - 0.5 * c1; break;
+        case LDSP_WIN_HAMMING: v[i] = 0.53836 - 0.46164 * c1; break;
+        default: v[i] = 0.35875 - 0.48829 * c1 + 0.14128 * c2 - 0.01168 * c3; break;
+        }
+    }
+    if (W == 1) v[0] = 1.0;
+    double e = 0.0;
+    for (double a : v) e += a * a;
+    const double g = 1.0 / sqrt(e);
+    std::vector<float> w(W);
+    for (unsigned i = 0; i < W; i++) w[i] = (float)(v[i] * g);
+    return w;
+}
+int ldsp_spgram_create(unsigned int nfft, int wtype, unsigned int W, unsigned int d, unsigned int A, ldsp_spgram_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        spgram_check_shape(nfft, W, d, A);
+        LDSP_REQUIRE(wtype >= LDSP_WIN_RECT && wtype <= LDSP_WIN_BLACKMANHARRIS, "spgram: unknown window type");
+        *q = spgram_make(nfft, W, d, A, spgram_window(wtype, W));
+    });
+}
+int ldsp_spgram_create_window(unsigned int nfft, const float* w, unsigned int W, unsigned int d, unsigned int A,
+                              ldsp_spgram_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        spgram_check_shape(nfft, W, d, A);
+        NONNULL(w);
+        *q = spgram_make(nfft, W, d, A, std::vector<float>(w, w + W));
+    });
+}
+int ldsp_spgram_destroy(ldsp_spgram_t q)
+{
+    return guard([&] {
+        if (q && q->last) (void)hipStreamSynchronize(q->last);
+        delete q;
+    });
+}
+static void spgram_quiesce(ldsp_spgram_s* q)
+{
+    if (q->last) LDSP_HIP(hipStreamSynchronize(q->last));
+    q->ord.sync();
+}
+int ldsp_spgram_reset(ldsp_spgram_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        q->seen = 0;
+        q->nacc = 0;
+        if (q->device < 0) return;
+        DeviceGuard g(q->device);
+        spgram_quiesce(q);
+        q->zero_stream();
+        q->zero_psd();
+    });
+}
+int ldsp_spgram_clear(ldsp_spgram_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        q->nacc = 0;
+        if (q->device < 0) return;
+        DeviceGuard g(q->device);
+        spgram_quiesce(q);
+        q->zero_psd();
+    });
+}
+int ldsp_spgram_get_info(ldsp_spgram_t q, unsigned int* nfft, unsigned int* W, unsigned int* d, unsigned int* A,
+                         uint64_t* samples, uint64_t* transforms)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (nfft) *nfft = q->N;
+        if (W) *W = q->W;
+        if (d) *d = q->d;
+        if (A) *A = q->A;
+        if (samples) *samples = q->seen;
+        if (transforms) *transforms = q->nacc;
+    });
+}
+int ldsp_spgram_get_window(ldsp_spgram_t q, float* w)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(w);
+        std::copy(q->w.begin(), q->w.end(), w);
+    });
+}
+int ldsp_spgram_num_outputs(ldsp_spgram_t q, size_t n, size_t* ntransforms, size_t* nrows)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (ntransforms) *ntransforms = q->transforms(n);
+        if (nrows) *nrows = q->rows(n);
+    });
+}
+// One piece of a call: launches, then the host-side state moves on.
+static void spgram_piece(ldsp_spgram_s* q, const void* dx, size_t n, float* dy, size_t dld, hipStream_t stream)
+{
+    const unsigned N = q->N;
+    const bool blocked = k::spgram_blocked(q->A);
+    const size_t A = blocked ? (size_t)k::kSpgramBlock : (size_t)q->A;   // transforms per row of the main kernel
+    const uint64_t s0 = q->seen / q->d, s1 = (q->seen + n) / q->d;
+    const size_t nt = (size_t)(s1 - s0);
+    const size_t nb = (size_t)(s1 / A - s0 / A);                         // its finished rows: blocks when blocked
+    k::SpgramCall c;
+    c.x = dx;
+    c.hist = q->hist[q->cur].p;
+    c.hist_out = q->hist[1 - q->cur].p;
+    c.n = n;
+    c.A = A;
+    c.a0 = (size_t)(s0 % A);
+    c.nt = nt;
+    c.ld = blocked ? N : dld;
+    c.base = (long long)((s0 + 1) * q->d - q->seen) - (long long)q->W;
+    c.W = (int)q->W;
+    c.d = (int)q->d;
+    c.win = q->dwin.as<float>();
+    c.tw = q->dtw.p;
+    c.carry_in = q->carry[q->ccur].as<float>();
+    c.carry_out = q->carry[1 - q->ccur].as<float>();
+    c.scale = blocked ? 1.0f : 1.0f / (float)q->A;
+    c.y = blocked ? (float*)q->blk.ensure(std::max<size_t>(nb, 1) * N * 4, q->device) : dy;
+    const size_t runs = k::spgram_runs((int)N, c.A, c.a0, nt, nullptr);
+    c.part = (float*)q->part.ensure(std::max<size_t>(runs, 1) * N * 4, q->device);
+    c.psd = q->dpsd.as<double>();
+    k::spgram((int)N, c, stream);
+    q->cur = 1 - q->cur;
+    // the unfinished row (block) moved to the other buffer if the piece left one behind
+    if (nt > 0 && s1 % A != 0) q->ccur = 1 - q->ccur;
+    if (blocked && nb > 0) {
+        const size_t M = q->A / A, c0 = (size_t)((s0 / A) % M);
+        k::spgram_rows((int)N, c.y, nb, M, c0, q->rcarry[q->rcur].as<float>(), q->rcarry[1 - q->rcur].as<float>(),
+                       q->A, dy, dld, stream);
+        if ((c0 + nb) % M != 0) q->rcur = 1 - q->rcur;
+    }
+    q->seen += n;
+    q->nacc += nt;
+}
+int ldsp_spgram_execute(ldsp_spgram_t q, const void* x, size_t n, float* y, size_t ld, size_t* nrows, int mem,
+                        void* stream)
+{
+    LDSP_RANGE("ldsp_spgram_execute");
+    return guard([&] {
+        NONNULL(q);
+        const size_t K = q->rows(n);
+        if (nrows) *nrows = K;
+        LDSP_REQUIRE(n == 0 || x, "spgram_execute: NULL input");
+        LDSP_REQUIRE(mem == LDSP_MEM_HOST || mem == LDSP_MEM_DEVICE, "mem must be LDSP_MEM_HOST or LDSP_MEM_DEVICE");
+        LDSP_REQUIRE(!y || ld >= q->N, "spgram_execute: row stride below nfft");
+        const BufDevice bd(mem, x);
+        const unsigned N = q->N;
+        if (q->device < 0) {
+            const int dev = current_device();
+            DeviceGuard g(dev);
+            std::vector<float> pad(q->w);
+            pad.resize(N, 0.0f);
+            upload(q->dwin, pad, dev);
+            std::vector<float> tw(2 * (size_t)N);             // exp(-2 pi i j / N): double, rounded once
+            for (unsigned j = 0; j < N; j++) {
+                const double a = -2.0 * M_PI * (double)j / (double)N;
+                tw[2 * j] = (float)cos(a);
+                tw[2 * j + 1] = (float)sin(a);
+            }
+            upload(q->dtw, tw, dev);
+            q->device = dev;
+            q->zero_stream();
+            q->zero_psd();
+        }
+        DeviceGuard g(q->device);
+        const Exec e = make_exec(q->device, mem, stream, bd);
+        q->ord.wait(e.stream);
+        // a host-memory call computes into a dense [K][N] device image
+        const bool rows_out = y != nullptr && K > 0;
+        const size_t dld = e.host ? N : ld;
+        const void* dx = q->stg.dev_in(e, x, n * 8);
+        float* const dy0 = rows_out ? (float*)q->stg.dev_out(e, y, K * (size_t)N * 4) : nullptr;
+        float* dy = dy0;
+        // a blocked average is taken in pieces of at most kSpgramMaxBlocks blocks
+        // (the block sums go through memory); the cut of a stream changes no bit
+        const size_t piece = k::spgram_blocked(q->A)
+                                 ? (size_t)q->d * k::kSpgramBlock * k::kSpgramMaxBlocks - (size_t)q->d * k::kSpgramBlock
+                                 : n;
+        for (size_t off = 0; off < n;) {
+            const size_t m = std::min(n - off, piece);
+            const size_t done = q->rows(m);
+            spgram_piece(q, (const char*)dx + off * 8, m, dy, dld, e.stream);
+            if (dy) dy += done * dld;
+            off += m;
+        }
+        q->ord.mark(e.stream);
+        q->last = e.stream;
+        if (e.host && rows_out && ld != N) {
+            // rows of the caller's image are ld floats apart
+            LDSP_HIP(hipMemcpy2DAsync(y, ld * 4, dy0, (size_t)N * 4, (size_t)N * 4, K, hipMemcpyDeviceToHost, e.stream));
+            LDSP_HIP(hipStreamSynchronize(e.stream));
+        } else {
+            q->stg.finish(e, y, rows_out ? K * (size_t)N * 4 : 0);
+        }
+    });
+}
+int ldsp_spgram_get_psd(ldsp_spgram_t q, double* psd, uint64_t* transforms)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(psd);
+        if (transforms) *transforms = q->nacc;
+        std::fill(psd, psd + q->N, 0.0);
+        if (q->nacc == 0 || q->device < 0) return;
+        DeviceGuard g(q->device);
+        spgram_quiesce(q);
+        LDSP_HIP(hipMemcpy(psd, q->dpsd.p, (size_t)q->N * 8, hipMemcpyDeviceToHost));
+        const double s = (double)q->nacc;
+        for (unsigned k = 0; k < q->N; k++) psd[k] /= s;
+    });
+}
+int ldsp_debug_spgram_tile(unsigned int nfft, size_t* transforms)
+{
+    return guard([&] {
+        NONNULL(transforms);
+        spgram_check_shape(nfft, 1, 1, 1);
+        *transforms = (size_t)k::spgram_tile((int)nfft);
     });
 }
 

@@ -400,6 +400,50 @@ struct ChanCall {
     void* y;
 };
 void chan(int M, int D, const ChanCall& c, hipStream_t s);
+// k_spgram.hip: streaming Welch periodogram (Spectrogram).  N = nfft (a power of
+// two, 256 .. 4096), window of W <= N taps, hop d <= W, A transforms per row.
+// x: n complex64 samples; hist / hist_out: the W - 1 samples before x[0] / before
+// the next call's x[0], distinct buffers; win: the window zero-padded to N
+// floats; tw[j] = exp(-2 pi i j / N), j < N.  The call takes nt transforms, the
+// first with its window starting at x[base] (base > -W), the next ones d samples
+// on; a0 of the first row's A transforms were taken by earlier calls, whose sum
+// is carry_in (float32[N]); a row the call does not finish leaves its sum in
+// carry_out (a distinct buffer).  Finished row r of the call, times scale, goes to y + r * ld
+// (y may be NULL: nothing is stored); every transform is added to psd (float64[N])
+// by way of part, room for spgram_runs() * N floats.  n = 0 launches nothing.
+constexpr int kSpgramMaxRuns = 2048;                  // workgroups of one call at the most
+constexpr int spgram_tile(int N) { return N >= 2048 ? 8 : 16384 / N; }   // transforms per workgroup
+struct SpgramCall {
+    const void* x;
+    const void* hist;
+    void* hist_out;
+    size_t n, A, a0, nt, ld;
+    long long base;
+    int W, d;
+    const float* win;
+    const void* tw;
+    const float* carry_in;
+    float* carry_out;
+    float scale;          // of a finished row's sum: 1 / A (1 for the block sums of a blocked average)
+    float* y;
+    float* part;
+    double* psd;
+};
+// workgroups (runs of whole rows) a call of nt transforms is cut into: rows of
+// spgram_tile(N) transforms together, more when that would pass kSpgramMaxRuns
+size_t spgram_runs(int N, size_t A, size_t a0, size_t nt, size_t* rows_per_run);
+void spgram(int N, const SpgramCall& c, hipStream_t s);
+// Blocked averages: A a multiple of kSpgramBlock and at least twice it.  spgram()
+// then runs with A = kSpgramBlock and y = blk (ld = N, nb finished blocks), and
+// spgram_rows adds the blocks of each row (M = A / kSpgramBlock of them, c0 of the
+// first row's taken by earlier calls and summed in carry_in) into y + r * ld, or
+// into carry_out for the row the call does not finish.  At most
+// kSpgramMaxBlocks / M + 1 rows per launch.
+constexpr int kSpgramBlock = 8;
+constexpr size_t kSpgramMaxBlocks = 16384;            // finished blocks of one spgram() + spgram_rows() pair
+constexpr bool spgram_blocked(size_t A) { return A >= 2 * kSpgramBlock && A % kSpgramBlock == 0; }
+void spgram_rows(int N, const float* blk, size_t nb, size_t M, size_t c0, const float* carry_in, float* carry_out,
+                 size_t A, float* y, size_t ld, hipStream_t s);
 struct FmState {          // FMStereo mixer loop state (device-resident)
     uint32_t theta, dtheta;
     float pe, alpha, beta;

@@ -1009,6 +1009,131 @@ struct Channelizer {
     }
 };
 
+// ------------------------------------------------------------------ Spectrogram (no reference counterpart)
+// Streaming Welch periodogram (ldsp.h): complex64[n] -> float32[rows, nfft], row
+// r the mean of `average` transforms' power per bin in FFT order, plus a running
+// float64 mean of every transform (psd).
+struct Spectrogram {
+    ldsp_spgram_t q = nullptr;
+    unsigned N = 0, W = 0, D = 0, A = 0;
+    Spectrogram(long nfft, const py::object& window, const py::object& window_len, const py::object& delay,
+                long average)
+    {
+        if (nfft < 0) throw py::value_error("Spectrogram: nfft must be a power of two");
+        const long wl = window_len.is_none() ? nfft : window_len.cast<long>();
+        if (wl < 0) throw py::value_error("Spectrogram: window_len must lie in 1 .. nfft");
+        const long d = delay.is_none() ? std::max(wl / 2, 1L) : delay.cast<long>();
+        if (d < 0) throw py::value_error("Spectrogram: delay must be at least 1");
+        if (average < 0) throw py::value_error("Spectrogram: average must be at least 1");
+        if (py::isinstance<py::str>(window)) {
+            const std::string name = window.cast<std::string>();
+            int wt = -1;
+            if (name == "rect") wt = LDSP_WIN_RECT;
+            else if (name == "hann") wt = LDSP_WIN_HANN;
+            else if (name == "hamming") wt = LDSP_WIN_HAMMING;
+            else if (name == "blackmanharris") wt = LDSP_WIN_BLACKMANHARRIS;
+            check(ldsp_spgram_create((unsigned)nfft, wt, (unsigned)wl, (unsigned)d, (unsigned)average, &q));
+        } else {
+            std::vector<float> w = to_fvec(window);
+            if ((long)w.size() != wl) throw py::value_error("Spectrogram: the window array's length must be window_len");
+            check(ldsp_spgram_create_window((unsigned)nfft, w.data(), (unsigned)wl, (unsigned)d, (unsigned)average, &q));
+        }
+        check(ldsp_spgram_get_info(q, &N, &W, &D, &A, nullptr, nullptr));
+    }
+    Spectrogram(const Spectrogram&) = delete;
+    ~Spectrogram()
+    {
+        if (q) ldsp_spgram_destroy(q);
+    }
+    void reset() { check(ldsp_spgram_reset(q)); }
+    void clear() { check(ldsp_spgram_clear(q)); }
+    py::array_t<float> window()
+    {
+        py::array_t<float> w(W);
+        check(ldsp_spgram_get_window(q, w.mutable_data()));
+        return w;
+    }
+    uint64_t num_samples()
+    {
+        uint64_t t = 0;
+        check(ldsp_spgram_get_info(q, nullptr, nullptr, nullptr, nullptr, &t, nullptr));
+        return t;
+    }
+    uint64_t num_transforms()
+    {
+        uint64_t t = 0;
+        check(ldsp_spgram_get_info(q, nullptr, nullptr, nullptr, nullptr, nullptr, &t));
+        return t;
+    }
+    size_t tile()
+    {
+        size_t f = 0;
+        check(ldsp_debug_spgram_tile(N, &f));
+        return f;
+    }
+    py::array_t<double> freqs()
+    {
+        py::array_t<double> c(N);
+        for (unsigned k = 0; k < N; k++) c.mutable_at(k) = std::fmod((double)k / N + 0.5, 1.0) - 0.5;
+        return c;
+    }
+    py::array_t<double> psd()
+    {
+        py::array_t<double> p(N);
+        double* pp = p.mutable_data();
+        int rc;
+        {
+            py::gil_scoped_release rel;
+            rc = ldsp_spgram_get_psd(q, pp, nullptr);
+        }
+        check(rc);
+        return p;
+    }
+    py::tuple num_outputs(size_t n)
+    {
+        size_t t = 0, r = 0;
+        check(ldsp_spgram_num_outputs(q, n, &t, &r));
+        return py::make_tuple(t, r);
+    }
+    // rows: store them and return the image; otherwise accumulate only and return the transforms taken
+    py::object run(const py::handle& x, bool rows)
+    {
+        size_t nt = 0, K = 0, nw = 0;
+        if (is_device_tensor(x)) {
+            DevIn d = dev_in(x, true);
+            check(ldsp_spgram_num_outputs(q, d.n, &nt, &K));
+            py::object out;
+            float* yp = nullptr;
+            if (rows) {
+                py::object& torch = torch_mod();
+                py::dict kw;
+                kw["dtype"] = torch.attr("float32");
+                kw["device"] = d.device;
+                out = torch.attr("empty")(py::make_tuple(K, N), **kw);
+                yp = (float*)tptr(out);
+            }
+            check(ldsp_spgram_execute(q, d.ptr, d.n, yp, N, &nw, LDSP_MEM_DEVICE, d.stream));
+            return rows ? out : py::object(py::int_(nt));
+        }
+        carr a = carr::ensure(x);
+        if (!a) throw py::error_already_set();
+        const size_t n = (size_t)a.size();
+        check(ldsp_spgram_num_outputs(q, n, &nt, &K));
+        py::array_t<float> out({(py::ssize_t)(rows ? K : 0), (py::ssize_t)N});
+        float* yp = rows ? out.mutable_data() : nullptr;
+        const void* xp = a.data();
+        int rc;
+        {
+            py::gil_scoped_release rel;
+            rc = ldsp_spgram_execute(q, xp, n, yp, N, &nw, LDSP_MEM_HOST, nullptr);
+        }
+        check(rc);
+        return rows ? py::object(out) : py::object(py::int_(nt));
+    }
+    py::object call(const py::handle& x) { return run(x, true); }
+    py::object write(const py::handle& x) { return run(x, false); }
+};
+
 // SSBDemod (demod.hpp:155-187): firhilbf_create(25, 60), c2r, one sideband kept
 struct SSBDemod {
     bool usb;
@@ -1617,6 +1742,28 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def_property_readonly("tile", &Channelizer::tile, "output columns per workgroup of the kernel")
         .def_property_readonly("centers", &Channelizer::centers, "channel centres k / nchan wrapped into [-0.5, 0.5)")
         .def("__call__", &Channelizer::call, "complex64[N] -> complex64[nchan, ncols]");
+
+    // ---- Spectrogram (beyond the reference: streaming Welch periodogram)
+    py::class_<Spectrogram>(m, "Spectrogram")
+        .def(py::init<long, py::object, py::object, py::object, long>(), py::arg("nfft"), py::arg("window") = "hann",
+             py::arg("window_len") = py::none(), py::arg("delay") = py::none(), py::arg("average") = 1)
+        .def("reset", &Spectrogram::reset, "zero the history, the counts, the unfinished row and the accumulator")
+        .def("clear", &Spectrogram::clear, "zero the accumulator and num_transforms only")
+        .def("num_outputs", &Spectrogram::num_outputs, py::arg("n"),
+             "(transforms, rows) the next call takes / returns for n input samples")
+        .def("write", &Spectrogram::write, "accumulate only; returns the transforms taken")
+        .def_property_readonly("nfft", [](Spectrogram& c) { return c.N; })
+        .def_property_readonly("window", &Spectrogram::window)
+        .def_property_readonly("window_len", [](Spectrogram& c) { return c.W; })
+        .def_property_readonly("delay", [](Spectrogram& c) { return c.D; })
+        .def_property_readonly("average", [](Spectrogram& c) { return c.A; })
+        .def_property_readonly("num_samples", &Spectrogram::num_samples, "input samples since creation or reset()")
+        .def_property_readonly("num_transforms", &Spectrogram::num_transforms,
+                               "transforms in psd: since creation, reset() or clear()")
+        .def_property_readonly("psd", &Spectrogram::psd, "float64[nfft]: mean power per bin over num_transforms")
+        .def_property_readonly("freqs", &Spectrogram::freqs, "bin centres k / nfft wrapped into [-0.5, 0.5)")
+        .def_property_readonly("tile", &Spectrogram::tile, "transforms per workgroup of the kernel")
+        .def("__call__", &Spectrogram::call, "complex64[n] -> float32[rows, nfft]");
 
     // ---- FreqDem (wrapper.cpp:183-187), BroadcastAM (wrapper.cpp:259-262)
     py::class_<FreqDem>(m, "FreqDem")
