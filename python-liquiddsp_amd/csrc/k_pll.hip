@@ -1435,12 +1435,19 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "v_cmp_gt_u32_e32 vcc, " X ", " W "\n\t"
 #endif
 // The lane-block transition.  The walker carries the serial chain and nothing else:
-// the next lane-block's offsets (v_mul_lo, quarter rate, then v_add3) are the critical
-// path into its VCCZ branch, so this lane-block's interval test -- sat((x - amin) -
-// awidth), kept in the lanes with x > W by a minimum with sat(x - W) (plain VALU: no
-// mask register, no exec switch) -- and the write of its final
-// offsets to xbuf[c & 1][lane-block][lane] are issued between the multiply and the add
-// (in-order issue: an instruction waiting on a result holds every later one).  The
+// the next lane-block's offsets (v_mul_lo, then v_add3) and their compare are the path
+// into its VCCZ branch.  This lane-block's interval test -- sat((x - amin) - awidth),
+// kept in the lanes with x > W by a minimum with sat(x - W) (plain VALU: no mask
+// register, no exec switch) -- costs its five issue slots wherever it stands (a lone
+// wave issues one VALU instruction per 4 clocks, dependent or not, and the multiply
+// hides none: scripts/ubench/walk_trans.hip D*, M*), so it keeps its place in front of
+// the add.  What moves is the LDS: the first LDS instruction behind a VALU one costs
+// ~12 clocks more than its slot and each one directly behind it 4 (N*), while the wait
+// for VCC between the compare and the branch holds LDS instructions for nothing (B2l).
+// So the write of the final offsets to xbuf[c & 1][lane-block][lane] stands behind the
+// compare, in one group with the reads of the next block's entries (TAIL), and no LDS
+// instruction is left between VALU ones (T0 -> T11: 92 -> 80 clocks per transition).
+// X stays live until the write has issued (the next lane-block writes XN, not X).  The
 // repaired outputs are stored and the repairs counted from xbuf by the loader waves
 // one block later (walk_help): no store offset, exec switch, store or count here.
 #define WL_LB(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)                           \
@@ -1459,9 +1466,9 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "v_sub_u32_e64 %[t], %[t], " E1W " clamp\n\t"                                                          \
     "v_min_u32 %[t], %[t], %[off]\n\t"                                                                     \
     "v_or_b32 %[acc], %[acc], %[t]\n\t"                                                                    \
-    "ds_write_b32 %[xs], " X " offset:" XO "\n\t"                                                          \
     "v_add3_u32 " XN ", " N0X ", %[kb], %[t2]\n\t"                                                         \
-    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t" TAIL
+    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t"                                                            \
+    "ds_write_b32 %[xs], " X " offset:" XO "\n\t" TAIL
 // block end: the other half of xbuf for the next block
 #define WL_XFLIP "v_sub_u32 %[xs], %[xsum], %[xs]\n\t"
 #define WL_NOFLIP ""
@@ -1540,6 +1547,83 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "s_mov_b64 exec, -1\n\t"                                                                               \
     "s_bcnt1_i32_b64 %[nr], %[pm]\n\t"                                                                     \
     "s_add_u32 %[nrep], %[nrep], %[nr]\n\t" TAIL
+// The transition as it stood before the LDS write moved behind the compare: all six
+// fillers between the multiply and the add (k_pll_walk VAR 320, with that commit's
+// block end; bitwise)
+#define WL_LB_SHADOW(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)  \
+    "s_cbranch_vccz 2f\n"                                                                                  \
+    "1:\n\t"                                                                                               \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccnz 1b\n"                                                    \
+    "3:\n\t"                                                                                               \
+    "s_mov_b64 exec, -1\n"                                                                                 \
+    "2:\n\t"                                                                                               \
+    "v_mul_lo_u32 %[t2], %[d], " SXN "\n\t"  \
+    "v_sub_u32_e64 %[off], " X ", " E0Y " clamp\n\t"  \
+    "v_sub_u32 %[t], " X ", " E0W "\n\t"  \
+    "v_sub_u32_e64 %[t], %[t], " E1W " clamp\n\t"  \
+    "v_min_u32 %[t], %[t], %[off]\n\t"  \
+    "v_or_b32 %[acc], %[acc], %[t]\n\t"  \
+    "ds_write_b32 %[xs], " X " offset:" XO "\n\t"  \
+    "v_add3_u32 " XN ", " N0X ", %[kb], %[t2]\n\t"  \
+    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t" TAIL
+// Orders tried beside the product's (bitwise): SPLIT (VAR 384) the test's last two
+// instructions behind the compare as well, in front of the LDS group; MID (VAR 416) the
+// write between the add and the compare
+#define WL_LB_SPLIT(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)  \
+    "s_cbranch_vccz 2f\n"                                                                                  \
+    "1:\n\t"                                                                                               \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccnz 1b\n"                                                    \
+    "3:\n\t"                                                                                               \
+    "s_mov_b64 exec, -1\n"                                                                                 \
+    "2:\n\t"                                                                                               \
+    "v_mul_lo_u32 %[t2], %[d], " SXN "\n\t"  \
+    "v_sub_u32 %[t], " X ", " E0W "\n\t"  \
+    "v_sub_u32_e64 %[off], " X ", " E0Y " clamp\n\t"  \
+    "v_sub_u32_e64 %[t], %[t], " E1W " clamp\n\t"  \
+    "v_add3_u32 " XN ", " N0X ", %[kb], %[t2]\n\t"  \
+    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t"  \
+    "v_min_u32 %[t], %[t], %[off]\n\t"  \
+    "v_or_b32 %[acc], %[acc], %[t]\n\t"  \
+    "ds_write_b32 %[xs], " X " offset:" XO "\n\t" TAIL
+#define WL_LB_MID(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)  \
+    "s_cbranch_vccz 2f\n"                                                                                  \
+    "1:\n\t"                                                                                               \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccz 3f\n\t"                                                  \
+    WX_REP(E1X, E1Y, E0Z, E0Y, X) "s_cbranch_vccnz 1b\n"                                                    \
+    "3:\n\t"                                                                                               \
+    "s_mov_b64 exec, -1\n"                                                                                 \
+    "2:\n\t"                                                                                               \
+    "v_mul_lo_u32 %[t2], %[d], " SXN "\n\t"  \
+    "v_sub_u32 %[t], " X ", " E0W "\n\t"  \
+    "v_sub_u32_e64 %[off], " X ", " E0Y " clamp\n\t"  \
+    "v_sub_u32_e64 %[t], %[t], " E1W " clamp\n\t"  \
+    "v_min_u32 %[t], %[t], %[off]\n\t"  \
+    "v_or_b32 %[acc], %[acc], %[t]\n\t"  \
+    "v_add3_u32 " XN ", " N0X ", %[kb], %[t2]\n\t"  \
+    "ds_write_b32 %[xs], " X " offset:" XO "\n\t"  \
+    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t" TAIL
+// The product's transition alone, every repair loop skipped (VAR 448, beside VAR 224:
+// the one of WL_LB_SHADOW; the test's result goes to a junk register)
+#define WL_LB_BARE(E0X, E0Y, E0Z, E0W, E1X, E1Y, E1Z, E1W, N0X, N0Y, SXN, X, XN, XO, TAIL)  \
+    "s_branch 2f\n"  \
+    "2:\n\t"  \
+    "v_mul_lo_u32 %[t2], %[d], " SXN "\n\t"  \
+    "v_sub_u32_e64 %[off], " X ", " E0Y " clamp\n\t"  \
+    "v_sub_u32 %[t], " X ", " E0W "\n\t"  \
+    "v_sub_u32_e64 %[t], %[t], " E1W " clamp\n\t"  \
+    "v_min_u32 %[t], %[t], %[off]\n\t"  \
+    "v_or_b32 v165, v165, %[t]\n\t"  \
+    "v_add3_u32 " XN ", " N0X ", %[kb], %[t2]\n\t"  \
+    "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t"  \
+    "ds_write_b32 %[xs], " X " offset:" XO "\n\t" TAIL
 // Timing variants of the product loop (tuning build, k_pll_walk VAR 32 / 64; wrong
 // outputs): NOREP skips every repair loop (the lane-block transitions, stores and
 // tests alone), NOST drops the store / interval test / repair count (loop + transitions).
@@ -1571,7 +1655,7 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
     "v_mul_lo_u32 %[t], %[d], " SXN "\n\t"                                                                 \
     "v_add3_u32 " XN ", " N0X ", %[kb], %[t]\n\t"                                                          \
     "v_cmp_gt_u32_e32 vcc, " XN ", " N0Y "\n\t" TAIL
-// HELPER (VAR 96): the product's lane-block (WL_LB) with the loader waves' deferred
+// HELPER (VAR 96): the lane-block of VAR 320 (WL_LB_SHADOW) with the loader waves' deferred
 // work left out -- what the helpers' LDS reads and stores cost the walker.  Timing
 // only: no repaired output is stored, no repair counted.
 // NOTEST (VAR 192): the same without any interval test in the transition (multiply,
@@ -1617,6 +1701,94 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
 #define WL_LBQ(LBM, a, b, c, d, e, f, g, h, n0, n1, n2, X, XN, XO, TAIL)                                         \
     LBM("v" #a, "v" #b, "v" #c, "v" #d, "v" #e, "v" #f, "v" #g, "v" #h, "v" #n0, "v" #n1, "v" #n2, X, XN, XO, TAIL)
 
+// Block end.  The verdict is a VALU -> SGPR -> SALU hand-off (~20 clocks before the
+// s_cmp may read `bad`: walk_trans.hip VSd), so what the failure exit does not read --
+// the rebase Kb += (S_{c+1} - S_c) D, the next slot, the zeroed accumulator, the other
+// half of xbuf (the caller forms slot, xs and Kb anew from c after a redo) -- is issued
+// in that wait, in front of the branch.  Behind it only the state of the next block's
+// start.  The next block's lane-block 7 entries are read behind the barrier, from the
+// slot address the transitions' reads used (ln, stepped to the next slot only then):
+// they are this wave's own prefetch and need no order with the loaders, and in front of
+// the barrier they put an LDS round trip (~50 clocks: walk_trans.hip Lrr) into its
+// s_waitcnt lgkmcnt(0), which now covers the xbuf write of lane-block 7 alone.  At
+// lane-block 7's lgkmcnt(13) these two reads, the header's and lane-block 0's three
+// are the oldest 6 of 24 in flight: 11 have returned.  KEEP: the bookkeeping of a loop
+// whose caller cannot read the previous block's slot any more (WL_KEEP_PREV; the store
+// base s4 of the loops that store on the walker stays with WL_BEND_PARENT).
+#define WL_BEND(FLIP, KEEP)                                                                                          \
+        "v_cmp_ne_u32_e64 %[bad], 0, %[acc]\n\t"                                                                      \
+        "v_mov_b32 %[acc], 0\n\t"                                                                                     \
+        FLIP                                                                                                          \
+        "s_mul_i32 %[tS], %[dS], %[d]\n\t"                                                                            \
+        "s_add_u32 %[kb], %[kb], %[tS]\n\t"                                                                           \
+        "s_add_u32 %[sn], %[sn], %[slot]\n\t"                                                                         \
+        "s_cmp_eq_u32 %[sn], %[rend]\n\t"                                                                             \
+        "s_cselect_b32 %[sn], %[ring], %[sn]\n\t"                                                                     \
+        "s_cmp_lg_u64 %[bad], 0\n\t"                                                                                  \
+        "s_cbranch_scc1 8f\n\t"                                                                                       \
+        KEEP                                                                                                          \
+        "s_mov_b32 %[S], %[snx]\n\t"                                                                                  \
+        "s_mov_b32 %[kb0], %[kb]\n\t"                                                                                 \
+        "s_mov_b32 %[d0], %[d]\n\t"                                                                                   \
+        "s_mov_b32 %[nrep0], %[nrep]\n\t"                                                                             \
+        "s_add_u32 %[c], %[c], 1\n\t"                                                                                 \
+        "s_waitcnt lgkmcnt(0)\n\t"                                                                                    \
+        "s_barrier\n\t"                                                                                               \
+        WL_PF(156:159, 160:163, 7168, 15360)                                                                          \
+        "v_mov_b32 %[lh], %[sn]\n\t"                                                                                  \
+        "v_add_u32 %[ln], %[sn], %[l16]\n\t"                                                                          \
+        "ds_read_b32 v164, %[lh] offset:16384\n\t"                                                                    \
+        "s_cmp_lt_u32 %[c], %[nblk]\n\t"                                                                              \
+        "s_cbranch_scc1 9b\n"
+#define WL_KEEP_PREV "v_mov_b32 %[s7], v158\n\t" "s_mov_b32 %[Sp], %[S]\n\t"
+#ifdef LDSP_TUNING
+// The block end as it stood before (k_pll_walk VAR 320 / 352 and the earlier variants,
+// whose recorded times it keeps comparable): the prefetch in front of the barrier,
+// all bookkeeping behind the verdict's branch
+#define WL_BEND_PARENT(FLIP)                                                                                          \
+        "v_cmp_ne_u32_e64 %[bad], 0, %[acc]\n\t"                                                                      \
+        "s_mul_i32 %[tS], %[dS], %[d]\n\t"                                                                            \
+        "s_cmp_lg_u64 %[bad], 0\n\t"                                                                                  \
+        "s_cbranch_scc1 8f\n\t"                                                                                       \
+        "v_mov_b32 %[s7], v158\n\t"                                                                                   \
+        WL_PF(156:159, 160:163, 7168, 15360)                                                                          \
+        "s_add_u32 %[kb], %[kb], %[tS]\n\t"                                                                           \
+        "s_mov_b32 %[Sp], %[S]\n\t"                                                                                   \
+        "s_mov_b32 %[S], %[snx]\n\t"                                                                                  \
+        "s_lshl_b32 %[s4], %[S], 2\n\t"                                                                               \
+        "s_mov_b32 %[kb0], %[kb]\n\t"                                                                                 \
+        "s_mov_b32 %[d0], %[d]\n\t"                                                                                   \
+        "s_mov_b32 %[nrep0], %[nrep]\n\t"                                                                             \
+        "v_mov_b32 %[acc], 0\n\t"                                                                                     \
+        FLIP                                                                                                          \
+        "s_add_u32 %[c], %[c], 1\n\t"                                                                                 \
+        "s_add_u32 %[sn], %[sn], %[slot]\n\t"                                                                         \
+        "s_cmp_eq_u32 %[sn], %[rend]\n\t"                                                                             \
+        "s_cselect_b32 %[sn], %[ring], %[sn]\n\t"                                                                     \
+        "s_waitcnt lgkmcnt(0)\n\t"                                                                                    \
+        "s_barrier\n\t"                                                                                               \
+        "v_mov_b32 %[lh], %[sn]\n\t"                                                                                  \
+        "v_add_u32 %[ln], %[sn], %[l16]\n\t"                                                                          \
+        "ds_read_b32 v164, %[lh] offset:16384\n\t"                                                                    \
+        "s_cmp_lt_u32 %[c], %[nblk]\n\t"                                                                              \
+        "s_cbranch_scc1 9b\n"
+#endif
+// Where the loop lies in the instruction cache decides 0.06 ms of a 1.3 ms walk: the
+// lone wave refills its instruction buffer after every taken branch, and the branch
+// taken once per lane-block with an event is the repair loop's exit to "3:", 212 bytes
+// into the lane-block.  A lane-block is 288 bytes (9 x 32), so one pad in front of the
+// loop places all eight: measured over the pads (profiles/walk_trans_ab.txt), "3:" on a
+// 32-byte boundary runs 1.281-1.287 ms, 4 bytes past it 1.303-1.309, 8 to 16 past it
+// 1.330-1.341, 20 to 24 past it 1.312-1.320.  Hence 64-byte alignment and 11 s_nop
+// (44 bytes) in front of "9:", executed once per entry of the statement: 44 + 212 = 256.
+// Whoever changes the length of WX_REP or of the lane-block's head re-derives the pad
+// (-DLDSP_WALK_PAD=n to sweep it).
+#ifndef LDSP_WALK_PAD
+#define LDSP_WALK_PAD 11
+#endif
+#define WL_STR2(x) #x
+#define WL_STR(x) WL_STR2(x)
+#define WL_ALIGN ".p2align 6\n\t.rept " WL_STR(LDSP_WALK_PAD) "\n\ts_nop 0\n\t.endr\n"
 #define WALK_ASM(LBM, BEND)                                                                                  \
     asm volatile(                                                                                                     \
         /* prologue: block c's entries, block c + 1's header, LB0's offsets / events */                               \
@@ -1647,7 +1819,8 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
         "s_waitcnt lgkmcnt(0)\n\t"                                                                                    \
         "v_mul_lo_u32 %[t], %[d], v102\n\t"                                                                           \
         "v_add3_u32 %[xa], v100, %[kb], %[t]\n\t"                                                                     \
-        "v_cmp_gt_u32_e32 vcc, %[xa], v101\n"                                                                         \
+        "v_cmp_gt_u32_e32 vcc, %[xa], v101\n\t"                                                                      \
+        WL_ALIGN                                                                                                      \
         "9:\n\t"                                                                                                      \
         WL_LBQ(LBM, 100, 101, 102, 103, 104, 105, 106, 107, 108, 109, 110, "%[xa]", "%[xb]", "0",                          \
                WL_PF(100:103, 104:107, 0, 8192))                                                                      \
@@ -1672,32 +1845,7 @@ __device__ __forceinline__ void walk_lb24(const uint4& E0, const uint4& E1, int 
         LBM("v156", "v157", "v158", "v159", "v160", "v161", "v162", "v163", "v100", "v101", "%[sx7]", "%[xb]",      \
               "%[xa]", "1792", "")                                                                                            \
         /* block end */                                                                                               \
-        "v_cmp_ne_u32_e64 %[bad], 0, %[acc]\n\t"                                                                      \
-        "s_mul_i32 %[tS], %[dS], %[d]\n\t"                                                                            \
-        "s_cmp_lg_u64 %[bad], 0\n\t"                                                                                  \
-        "s_cbranch_scc1 8f\n\t"                                                                                       \
-        "v_mov_b32 %[s7], v158\n\t"                                                                                   \
-        WL_PF(156:159, 160:163, 7168, 15360)                                                                          \
-        "s_add_u32 %[kb], %[kb], %[tS]\n\t"                                                                           \
-        "s_mov_b32 %[Sp], %[S]\n\t"                                                                                   \
-        "s_mov_b32 %[S], %[snx]\n\t"                                                                                  \
-        "s_lshl_b32 %[s4], %[S], 2\n\t"                                                                               \
-        "s_mov_b32 %[kb0], %[kb]\n\t"                                                                                 \
-        "s_mov_b32 %[d0], %[d]\n\t"                                                                                   \
-        "s_mov_b32 %[nrep0], %[nrep]\n\t"                                                                             \
-        "v_mov_b32 %[acc], 0\n\t"                                                                                     \
         BEND                                                                                                          \
-        "s_add_u32 %[c], %[c], 1\n\t"                                                                                 \
-        "s_add_u32 %[sn], %[sn], %[slot]\n\t"                                                                         \
-        "s_cmp_eq_u32 %[sn], %[rend]\n\t"                                                                             \
-        "s_cselect_b32 %[sn], %[ring], %[sn]\n\t"                                                                     \
-        "s_waitcnt lgkmcnt(0)\n\t"                                                                                    \
-        "s_barrier\n\t"                                                                                               \
-        "v_mov_b32 %[lh], %[sn]\n\t"                                                                                  \
-        "v_add_u32 %[ln], %[sn], %[l16]\n\t"                                                                          \
-        "ds_read_b32 v164, %[lh] offset:16384\n\t"                                                                    \
-        "s_cmp_lt_u32 %[c], %[nblk]\n\t"                                                                              \
-        "s_cbranch_scc1 9b\n"                                                                                         \
         "8:\n\t"                                                                                                      \
         "s_waitcnt lgkmcnt(0)"                                                                                        \
         : [xa] "=&v"(xa), [xb] "=&v"(xb), [t] "=&v"(t), [t2] "=&v"(t2), [off] "=&v"(off), [acc] "=&v"(acc),          \
@@ -1727,9 +1875,14 @@ struct WalkLoop {
 // Runs blocks c .. nblk - 1 until one fails its interval test (returns with c = that
 // block, not yet barriered) or all are done (c = nblk).  xb0: this lane's word of
 // xbuf[0][0].  PV: 0 the product; the tuning build's variants: 1 / 2 WL_LB_NOREP /
-// WL_LB_NOST, 3 the product's loop (without the helpers' work), 4 / 5 / 9 earlier loops
+// WL_LB_NOST, 3 the loop of 10 without the helpers' work, 4 / 5 / 9 earlier loops
 // that store and count on the walker (WL_LB_ORIG / WL_LB_PRE / WL_LB_PARENT), 6 - 8
-// WL_LB_NOTEST / WL_LB_HELPER_NOREP / WL_LB_NOTEST_NOREP.
+// WL_LB_NOTEST / WL_LB_HELPER_NOREP / WL_LB_NOTEST_NOREP; with the helpers, bitwise: 10
+// the loop before the LDS write moved behind the compare (WL_LB_SHADOW, WL_BEND_PARENT),
+// 11 / 15 the product's transition with that block end / that transition with the
+// product's block end, 12 / 13 WL_LB_SPLIT / WL_LB_MID; 14 WL_LB_BARE (timing only).
+// w.s7 / w.Sprev are kept by the loops of WL_BEND_PARENT and WL_KEEP_PREV alone: the
+// product's caller reads them from the previous block's slot when a block fails.
 template <int PV>
 __device__ __forceinline__ void walk_asm_loop(WalkLoop& w, uint32_t nblk, uint32_t ring, float* y, uint32_t lane16,
                                               uint32_t xb0)
@@ -1746,27 +1899,39 @@ __device__ __forceinline__ void walk_asm_loop(WalkLoop& w, uint32_t nblk, uint32
     unsigned long long pm, bad;
     uint32_t kb = w.kb, d = w.d, nrep = w.nrep, c = w.c, S = w.S, Sprev = w.Sprev, kb0, d0, nrep0;
     if constexpr (PV == 0) {
-        WALK_ASM(WL_LB, WL_XFLIP);
+        WALK_ASM(WL_LB, WL_BEND(WL_XFLIP, ""));
     }
 #ifdef LDSP_TUNING
     else if constexpr (PV == 1) {
-        WALK_ASM(WL_LB_NOREP, WL_NOFLIP);
+        WALK_ASM(WL_LB_NOREP, WL_BEND_PARENT(WL_NOFLIP));
     } else if constexpr (PV == 2) {
-        WALK_ASM(WL_LB_NOST, WL_NOFLIP);
+        WALK_ASM(WL_LB_NOST, WL_BEND_PARENT(WL_NOFLIP));
     } else if constexpr (PV == 4) {
-        WALK_ASM(WL_LB_ORIG, WL_NOFLIP);
+        WALK_ASM(WL_LB_ORIG, WL_BEND_PARENT(WL_NOFLIP));
     } else if constexpr (PV == 5) {
-        WALK_ASM(WL_LB_PRE, WL_NOFLIP);
+        WALK_ASM(WL_LB_PRE, WL_BEND_PARENT(WL_NOFLIP));
     } else if constexpr (PV == 3) {
-        WALK_ASM(WL_LB, WL_XFLIP);
+        WALK_ASM(WL_LB_SHADOW, WL_BEND_PARENT(WL_XFLIP));
     } else if constexpr (PV == 6) {
-        WALK_ASM(WL_LB_NOTEST, WL_XFLIP);
+        WALK_ASM(WL_LB_NOTEST, WL_BEND_PARENT(WL_XFLIP));
     } else if constexpr (PV == 7) {
-        WALK_ASM(WL_LB_HELPER_NOREP, WL_XFLIP);
+        WALK_ASM(WL_LB_HELPER_NOREP, WL_BEND_PARENT(WL_XFLIP));
     } else if constexpr (PV == 8) {
-        WALK_ASM(WL_LB_NOTEST_NOREP, WL_XFLIP);
+        WALK_ASM(WL_LB_NOTEST_NOREP, WL_BEND_PARENT(WL_XFLIP));
+    } else if constexpr (PV == 9) {
+        WALK_ASM(WL_LB_PARENT, WL_BEND_PARENT(WL_NOFLIP));
+    } else if constexpr (PV == 10) {
+        WALK_ASM(WL_LB_SHADOW, WL_BEND_PARENT(WL_XFLIP));
+    } else if constexpr (PV == 11) {
+        WALK_ASM(WL_LB, WL_BEND_PARENT(WL_XFLIP));
+    } else if constexpr (PV == 12) {
+        WALK_ASM(WL_LB_SPLIT, WL_BEND(WL_XFLIP, ""));
+    } else if constexpr (PV == 13) {
+        WALK_ASM(WL_LB_MID, WL_BEND(WL_XFLIP, ""));
+    } else if constexpr (PV == 14) {
+        WALK_ASM(WL_LB_BARE, WL_BEND(WL_XFLIP, WL_KEEP_PREV));
     } else {
-        WALK_ASM(WL_LB_PARENT, WL_NOFLIP);
+        WALK_ASM(WL_LB_SHADOW, WL_BEND(WL_XFLIP, ""));
     }
 #endif
     w.c = c;
@@ -1810,7 +1975,7 @@ __device__ __forceinline__ void k_pll_walk_body(PllIn in, long n, AmpState* st, 
     __shared__ uint32_t hcount;          // repairs counted by the loader waves
     // the product path's loop stores and counts on the loader waves (HELP); earlier
     // loops of the tuning build on the walker (WSTORE), the timing-only ones nowhere
-    constexpr bool HELP = F24 && !STATS && VAR == 0;
+    constexpr bool HELP = F24 && !STATS && (VAR == 0 || VAR == 320 || VAR == 352 || VAR == 384 || VAR == 416 || VAR == 480);
     constexpr bool WSTORE = VAR == 32 || VAR == 64 || VAR == 128 || VAR == 160 || VAR == 288;
     // HELP reads block c - 1's slot during block c, so its DMA reuses the slot of block
     // c - 2: one block less ahead
@@ -1888,7 +2053,8 @@ __device__ __forceinline__ void k_pll_walk_body(PllIn in, long n, AmpState* st, 
     unsigned long long cyc_undo = 0, cyc_fb = 0;      // product loop's block redos: undo pass, fallback lane-blocks
 #endif
     static_assert(VAR == 0 || VAR == 32 || VAR == 64 || VAR == 96 || VAR == 128 || VAR == 160 || VAR == 192 ||
-                      VAR == 224 || VAR == 256 || VAR == 288,
+                      VAR == 224 || VAR == 256 || VAR == 288 || VAR == 320 || VAR == 352 || VAR == 384 || VAR == 416 ||
+                      VAR == 448 || VAR == 480,
                   "walker variant");
     if constexpr (F24 && !STATS) {
         // the product path: the block loop in one asm statement (walk_asm_loop)
@@ -1927,8 +2093,19 @@ __device__ __forceinline__ void k_pll_walk_body(PllIn in, long n, AmpState* st, 
                 w.S = Sn;
                 walk_asm_loop<VAR / 32>(w, (uint32_t)nblk, ring, y, (uint32_t)lane * 16u,
                                         (uint32_t)(uintptr_t)&xbuf[0][0][lane]);
-                if (w.c > c0) prev = PrevLB{w.s7, 64, w.Sprev, false};
                 if (w.c >= (uint32_t)nblk) break;
+                if (w.c > c0) {
+                    // the last lane-block of the block before the failed one (walk_fallback's
+                    // first sample).  With the helpers that block's slot is intact until the
+                    // barrier ending block c (the DMA reuses the slot of block c - 2), so the
+                    // product's loop carries neither register through its block end.
+                    if constexpr (HELP) {
+                        const WalkBufE& pb = buf[(w.c - 1) % kRing];
+                        prev = PrevLB{pb.e[0][(kBlkE / 64 - 1) * 64 + lane].z, 64, rfl(pb.hdr[0]), false};
+                    } else {
+                        prev = PrevLB{w.s7, 64, w.Sprev, false};
+                    }
+                }
 #ifdef LDSP_TUNING
                 const unsigned long long tf0 = wall_clock64();      // fallback cost (stats[2], stats[3])
 #endif
@@ -2326,6 +2503,12 @@ void pll_back(const PllCall& c, hipStream_t s)
                 case 224: WALK_LAUNCH(true, false, 224); break;
                 case 256: WALK_LAUNCH(true, false, 256); break;
                 case 288: WALK_LAUNCH(true, false, 288); break;
+                case 320: WALK_LAUNCH(true, false, 320); break;
+                case 352: WALK_LAUNCH(true, false, 352); break;
+                case 384: WALK_LAUNCH(true, false, 384); break;
+                case 416: WALK_LAUNCH(true, false, 416); break;
+                case 448: WALK_LAUNCH(true, false, 448); break;
+                case 480: WALK_LAUNCH(true, false, 480); break;
                 default: break;
                 }
                 return;
