@@ -551,6 +551,48 @@ int ldsp_chan_execute(ldsp_chan_t q, const void *x, size_t n, void *y, size_t ld
 int ldsp_debug_chan_tile(unsigned int M, unsigned int D, size_t *frames);
 
 /* ------------------------------------------------------------------------
+ * Synthesizer: a polyphase synthesis filter bank, M channel rows to one
+ * dense complex64 stream in one pass; the Channelizer's counterpart.  The
+ * definition is this library's own.  Column n and output sample t are absolute
+ * indices since creation or reset (zeros before column 0); g is a real
+ * prototype of L taps, M the channel count and D the interpolation:
+ *   z[t] = scale sum_{k<M} sum_{n : 0 <= t - nD < L} g[t - nD] y[k][n] exp(+2 pi i k t / M)
+ * i.e. zero-stuff every row by D, filter with g, mix row k up to k / M cycles
+ * per sample with the phase tied to absolute t, and sum the rows.  A call of
+ * ncols columns returns exactly ncols * D samples (ncols = 0 is allowed); a
+ * stream of columns may be cut into calls anywhere without changing a bit.
+ *   M: a power of two, 4 <= M <= 256;  D = M (critically sampled) or M / 2 (2x
+ *   oversampled);  at most 17 taps per branch (L <= 17 M; m <= 8).
+ * ldsp_synth_create designs g = firdes_kaiser(2 M m + 1, fc, as, 0) (fc <= 0:
+ * 1 / M at D = M / 2, 0.5 / M at D = M) and sets scale = D / sum(g);
+ * ldsp_synth_create_taps takes g as given with scale = 1.  With the defaults
+ * at D = M / 2, ldsp_chan_create(M, M / 2, m, 0, as) followed by
+ * ldsp_synth_create(M, M / 2, m, 0, as) reproduces the input delayed by
+ * L - 1 = 2 M m samples, to the prototype's stop-band level 10^(-as / 20).
+ * The error codes are the Channelizer's: a non-power-of-two M, M < 4, another
+ * D, m = 0, L = 0, as <= 0 and fc >= 0.5 are LDSP_EINVAL; a power-of-two M
+ * above 256 and more than 17 taps per branch are LDSP_EUNSUP.
+ * ldsp_synth_execute reads row k at y + k * ld (ld in samples; ld < ncols is
+ * LDSP_EINVAL) and writes ncols * D samples to z; it sets *n and, when
+ * cap < *n, returns LDSP_ERANGE without consuming the input.  Argument errors
+ * are decided on the host before any device work.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_synth_s *ldsp_synth_t;
+int ldsp_synth_create(unsigned int M, unsigned int D, unsigned int m, float fc, float as, ldsp_synth_t *q);
+int ldsp_synth_create_taps(unsigned int M, unsigned int D, const float *g, unsigned int L, ldsp_synth_t *q);
+int ldsp_synth_destroy(ldsp_synth_t q);
+int ldsp_synth_reset(ldsp_synth_t q);
+int ldsp_synth_get_info(ldsp_synth_t q, unsigned int *M, unsigned int *D, unsigned int *L);   /* any may be NULL */
+int ldsp_synth_get_taps(ldsp_synth_t q, float *g);               /* L floats */
+int ldsp_synth_get_scale(ldsp_synth_t q, float *s);
+int ldsp_synth_set_scale(ldsp_synth_t q, float s);
+int ldsp_synth_num_outputs(ldsp_synth_t q, size_t ncols, size_t *n);
+int ldsp_synth_execute(ldsp_synth_t q, const void *y, size_t ld, size_t ncols, void *z, size_t cap, size_t *n,
+                       int mem, void *stream);
+/* Test hook: input columns per workgroup of the (M, D) kernel. */
+int ldsp_debug_synth_tile(unsigned int M, unsigned int D, size_t *cols);
+
+/* ------------------------------------------------------------------------
  * Spectrogram: a streaming Welch periodogram, one complex64 stream to rows of
  * power per bin and a running mean of them.  No reference counterpart
  * (liquid's spgramcf / spwaterfallcf are the same block: a zeroed window

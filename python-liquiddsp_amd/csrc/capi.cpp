@@ -1194,6 +1194,28 @@ struct ldsp_chan_s {
     }
 };
 
+// Synthesizer (polyphase synthesis bank): the prototype, the host-side column
+// count (the D = M / 2 sign's parity follows from it), and on the device the
+// padded taps, the twiddle table and the last Q - 1 input columns as
+// [M][Q - 1], ping-ponged.
+struct ldsp_synth_s {
+    unsigned int M = 0, D = 0, Q = 0;
+    std::vector<float> g;
+    float scale = 1.0f;
+    uint64_t seen = 0;                     // input columns since create / reset
+    int device = -1, cur = 0;
+    ldsp::DevBuf dtaps, dtw, hist[2];
+    hipStream_t last = nullptr;
+    ldsp::StreamMark ord;
+    ldsp::Staging stg;
+    size_t hist_bytes() const { return std::max<size_t>((size_t)M * (Q - 1), 1) * 8; }
+    void zero()
+    {
+        for (auto& b : hist) ldsp::zero_now(b.ensure(hist_bytes(), device), 0, hist_bytes());
+        cur = 0;
+    }
+};
+
 // Spectrogram (streaming Welch periodogram): the window, the host-side counts
 // (samples since reset, transforms since clear; the schedule follows from
 // them), and on the device the padded window, the twiddle table, the last
@@ -3228,6 +3250,17 @@ int ldsp_debug_firhilb_tile(int op, size_t* samples)
 }
 
 // ---------------------------------------------------------------- Channelizer
+// exp(2 pi i j / M), j < M, as (re, im) pairs: double, rounded once (k_chan, k_synth)
+static std::vector<float> bank_twiddles(unsigned int M)
+{
+    std::vector<float> tw(2 * (size_t)M);
+    for (unsigned j = 0; j < M; j++) {
+        const double a = 2.0 * M_PI * (double)j / (double)M;
+        tw[2 * j] = (float)cos(a);
+        tw[2 * j + 1] = (float)sin(a);
+    }
+    return tw;
+}
 static void chan_check_shape(unsigned int M, unsigned int D)
 {
     LDSP_REQUIRE(M >= 4 && (M & (M - 1)) == 0, "chan: the channel count must be a power of two, at least 4");
@@ -3343,13 +3376,7 @@ int ldsp_chan_execute(ldsp_chan_t q, const void* x, size_t n, void* y, size_t ld
             std::vector<float> pad(q->h);
             pad.resize((size_t)k::kChanMaxP * M, 0.0f);
             upload(q->dtaps, pad, dev);
-            std::vector<float> tw(2 * (size_t)M);             // exp(2 pi i j / M): double, rounded once
-            for (unsigned j = 0; j < M; j++) {
-                const double a = 2.0 * M_PI * (double)j / (double)M;
-                tw[2 * j] = (float)cos(a);
-                tw[2 * j + 1] = (float)sin(a);
-            }
-            upload(q->dtw, tw, dev);
+            upload(q->dtw, bank_twiddles(M), dev);
             q->device = dev;
             q->zero();
         }
@@ -3397,6 +3424,174 @@ int ldsp_debug_chan_tile(unsigned int M, unsigned int D, size_t* frames)
         chan_check_shape(M, D);
         if (M > 256) throw Error(LDSP_EUNSUP, "chan: more than 256 channels is not implemented");
         *frames = (size_t)k::chan_frames((int)M);
+    });
+}
+
+// ---------------------------------------------------------------- Synthesizer
+static void synth_check_shape(unsigned int M, unsigned int D)
+{
+    LDSP_REQUIRE(M >= 4 && (M & (M - 1)) == 0, "synth: the channel count must be a power of two, at least 4");
+    LDSP_REQUIRE(D == M || 2 * D == M, "synth: the interpolation must be M (critically sampled) or M / 2 (2x oversampled)");
+}
+static ldsp_synth_s* synth_make(unsigned int M, unsigned int D, std::vector<float> g, float scale)
+{
+    if (M > 256) throw Error(LDSP_EUNSUP, "synth: more than 256 channels is not implemented");
+    if (g.size() > (size_t)k::kChanMaxP * M)
+        throw Error(LDSP_EUNSUP, "synth: more than " + std::to_string(k::kChanMaxP) + " taps per branch (L > " +
+                                     std::to_string(k::kChanMaxP) + " M) is not implemented");
+    std::unique_ptr<ldsp_synth_s> o(new ldsp_synth_s());
+    o->M = M;
+    o->D = D;
+    o->Q = (unsigned)((g.size() + D - 1) / D);
+    o->g = std::move(g);
+    o->scale = scale;
+    return o.release();
+}
+int ldsp_synth_create(unsigned int M, unsigned int D, unsigned int m, float fc, float as, ldsp_synth_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        synth_check_shape(M, D);
+        LDSP_REQUIRE(m >= 1, "synth: filter semi-length must be at least 1");
+        LDSP_REQUIRE(as > 0.0f, "synth: stop-band attenuation must be > 0");
+        LDSP_REQUIRE(fc < 0.5f, "synth: cutoff must be below 0.5");
+        if (M > 256) throw Error(LDSP_EUNSUP, "synth: more than 256 channels is not implemented");
+        if (2 * (size_t)m + 1 > (size_t)k::kChanMaxP)
+            throw Error(LDSP_EUNSUP, "synth: semi-length above " + std::to_string((k::kChanMaxP - 1) / 2) +
+                                         " is not implemented");
+        // D = M / 2: flat across the analysis prototype's transition band, stopped before the image at 2 / M
+        if (!(fc > 0.0f)) fc = (D == M ? 0.5f : 1.0f) / (float)M;
+        std::vector<float> g = design::firdes_kaiser(2 * M * m + 1, fc, as, 0.0f);
+        double sum = 0.0;
+        for (float v : g) sum += (double)v;
+        *q = synth_make(M, D, std::move(g), (float)((double)D / sum));
+    });
+}
+int ldsp_synth_create_taps(unsigned int M, unsigned int D, const float* g, unsigned int L, ldsp_synth_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        synth_check_shape(M, D);
+        LDSP_REQUIRE(L >= 1, "synth: at least one tap");
+        NONNULL(g);
+        *q = synth_make(M, D, std::vector<float>(g, g + L), 1.0f);
+    });
+}
+int ldsp_synth_destroy(ldsp_synth_t q)
+{
+    return guard([&] {
+        if (q && q->last) (void)hipStreamSynchronize(q->last);
+        delete q;
+    });
+}
+int ldsp_synth_reset(ldsp_synth_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        q->seen = 0;
+        if (q->device < 0) return;
+        DeviceGuard g(q->device);
+        if (q->last) LDSP_HIP(hipStreamSynchronize(q->last));
+        q->ord.sync();
+        q->zero();
+    });
+}
+int ldsp_synth_get_info(ldsp_synth_t q, unsigned int* M, unsigned int* D, unsigned int* L)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (M) *M = q->M;
+        if (D) *D = q->D;
+        if (L) *L = (unsigned)q->g.size();
+    });
+}
+int ldsp_synth_get_taps(ldsp_synth_t q, float* g)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(g);
+        std::copy(q->g.begin(), q->g.end(), g);
+    });
+}
+int ldsp_synth_get_scale(ldsp_synth_t q, float* s) { return guard([&] { NONNULL(q); NONNULL(s); *s = q->scale; }); }
+int ldsp_synth_set_scale(ldsp_synth_t q, float s) { return guard([&] { NONNULL(q); q->scale = s; }); }
+int ldsp_synth_num_outputs(ldsp_synth_t q, size_t ncols, size_t* n)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(n);
+        *n = ncols * q->D;
+    });
+}
+int ldsp_synth_execute(ldsp_synth_t q, const void* y, size_t ld, size_t ncols, void* z, size_t cap, size_t* n, int mem,
+                       void* stream)
+{
+    LDSP_RANGE("ldsp_synth_execute");
+    return guard([&] {
+        NONNULL(q);
+        const unsigned M = q->M, D = q->D;
+        const size_t K = ncols, N = K * D;
+        if (n) *n = N;
+        LDSP_REQUIRE(ld >= K, "synth_execute: row stride below the number of columns");
+        if (cap < N) throw Error(LDSP_ERANGE, "synth_execute: output capacity below ncols * D");
+        LDSP_REQUIRE(K == 0 || y, "synth_execute: NULL input");
+        LDSP_REQUIRE(K == 0 || z, "synth_execute: NULL output");
+        LDSP_REQUIRE(mem == LDSP_MEM_HOST || mem == LDSP_MEM_DEVICE, "mem must be LDSP_MEM_HOST or LDSP_MEM_DEVICE");
+        const BufDevice bd(mem, y);
+        if (q->device < 0) {
+            const int dev = current_device();
+            DeviceGuard g(dev);
+            std::vector<float> pad(q->g);
+            pad.resize((size_t)k::kChanMaxP * M, 0.0f);
+            upload(q->dtaps, pad, dev);
+            upload(q->dtw, bank_twiddles(M), dev);
+            q->device = dev;
+            q->zero();
+        }
+        DeviceGuard g(q->device);
+        const Exec e = make_exec(q->device, mem, stream, bd);
+        q->ord.wait(e.stream);
+        // a host-memory call reads a dense [M][K] device image
+        const size_t dld = e.host ? K : ld;
+        const void* dy;
+        if (e.host && ld != K && K > 0) {
+            // rows of the caller's image are ld samples apart
+            void* in = q->stg.in.ensure((size_t)M * K * 8, e.device);
+            LDSP_HIP(hipMemcpy2DAsync(in, K * 8, y, ld * 8, K * 8, M, hipMemcpyHostToDevice, e.stream));
+            dy = in;
+        } else {
+            dy = q->stg.dev_in(e, y, (size_t)M * K * 8);
+        }
+        void* dz = q->stg.dev_out(e, z, N * 8);
+        if (K > 0) {
+            k::SynthCall c;
+            c.y = dy;
+            c.hist = q->hist[q->cur].p;
+            c.hist_out = q->hist[1 - q->cur].p;
+            c.ncols = K;
+            c.ld = dld;
+            c.parity = (int)(q->seen & 1);
+            c.Q = (int)q->Q;
+            c.taps = q->dtaps.as<float>();
+            c.tw = q->dtw.p;
+            c.scale = q->scale;
+            c.z = dz;
+            k::synth((int)M, (int)D, c, e.stream);
+            q->cur = 1 - q->cur;
+            q->seen += K;
+        }
+        q->ord.mark(e.stream);
+        q->last = e.stream;
+        q->stg.finish(e, z, N * 8);
+    });
+}
+int ldsp_debug_synth_tile(unsigned int M, unsigned int D, size_t* cols)
+{
+    return guard([&] {
+        NONNULL(cols);
+        synth_check_shape(M, D);
+        if (M > 256) throw Error(LDSP_EUNSUP, "synth: more than 256 channels is not implemented");
+        *cols = (size_t)k::synth_cols((int)M);
     });
 }
 

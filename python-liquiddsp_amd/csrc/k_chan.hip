@@ -31,7 +31,7 @@
 // tile or a call, so an output's bits do not depend on the cut of the stream.
 // Workgroup 0 also writes the next call's history (the last P M - 1 samples of
 // history ++ input) into the other buffer of the pair.
-#include "fft_butterflies.hpp"
+#include "chan_dft.hpp"
 #include "kernels.hpp"
 #include "ldsp_common.hpp"
 
@@ -40,28 +40,11 @@ namespace k {
 
 namespace {
 
-constexpr int chan_r2(int M) { return M <= 16 ? 1 : (M <= 64 ? 8 : 16); }
 constexpr int chan_slots(int M, int D)
 {
     const int F = chan_frames(M);
     const int xs = (F - 1) * D + kChanMaxP * M, us = F * (M + 1);
     return xs > us ? xs : us;
-}
-
-// inverse R-point DFT in place, natural order: the forward one read at (R - k) mod R
-template <int R>
-__device__ __forceinline__ void chan_idft(float2 (&v)[R])
-{
-    static_assert(R == 4 || R == 8 || R == 16, "register transforms: 4, 8, 16 points");
-    if constexpr (R == 4) dft4(v[0], v[1], v[2], v[3]);
-    else if constexpr (R == 8) dft8(v);
-    else dft16(v);
-#pragma unroll
-    for (int k = 1; k < R / 2; k++) {
-        const float2 t = v[k];
-        v[k] = v[R - k];
-        v[R - k] = t;
-    }
 }
 
 // n: input samples of the call (> 0); skip: samples before the call's first

@@ -400,6 +400,29 @@ struct ChanCall {
     void* y;
 };
 void chan(int M, int D, const ChanCall& c, hipStream_t s);
+// k_synth.hip: polyphase synthesis filter bank (Synthesizer), k_chan's
+// counterpart.  M rows (a power of two, 4 .. 256), interpolation D = M or M / 2,
+// Q = ceil(L / D) <= synth_qmax(M, D) taps per output residue.  y: row k at
+// y + k * ld, ncols columns of complex64; hist / hist_out: the Q - 1 columns
+// before the call's first / before the next call's first as [M][Q - 1],
+// distinct buffers (at least one readable sample when Q = 1); taps: the
+// prototype zero-padded to kChanMaxP * M floats; tw as k_chan's; parity: that of
+// the first column's absolute index (the D = M / 2 sign).  z receives
+// ncols * D samples.  ncols = 0 launches nothing.
+constexpr int synth_qmax(int M, int D) { return kChanMaxP * (M / D); }
+constexpr int synth_cols(int M) { return chan_frames(M); }            // input columns per workgroup
+struct SynthCall {
+    const void* y;
+    const void* hist;
+    void* hist_out;
+    size_t ncols, ld;
+    int parity, Q;
+    const float* taps;
+    const void* tw;
+    float scale;
+    void* z;
+};
+void synth(int M, int D, const SynthCall& c, hipStream_t s);
 // k_spgram.hip: streaming Welch periodogram (Spectrogram).  N = nfft (a power of
 // two, 256 .. 4096), window of W <= N taps, hop d <= W, A transforms per row.
 // x: n complex64 samples; hist / hist_out: the W - 1 samples before x[0] / before

@@ -1009,6 +1009,123 @@ struct Channelizer {
     }
 };
 
+// ------------------------------------------------------------------ Synthesizer (no reference counterpart)
+// Polyphase synthesis bank (ldsp.h): complex64[nchan, K] -> complex64[K * interp],
+// row k mixed up to k / nchan.  A device tensor whose columns are contiguous (a
+// block of rows or a range of columns of a Channelizer output) is read in place.
+struct Synthesizer {
+    ldsp_synth_t q = nullptr;
+    unsigned M = 0, D = 0, L = 0;
+    Synthesizer(int nchan, const py::object& interp, int m, const py::object& fc, float as, const py::object& taps)
+    {
+        if (nchan < 0) throw py::value_error("Synthesizer: nchan must be a power of two, at least 4");
+        const int d = interp.is_none() ? nchan / 2 : interp.cast<int>();
+        if (d < 0) throw py::value_error("Synthesizer: interp must be nchan or nchan // 2");
+        if (!taps.is_none()) {
+            std::vector<float> g = to_fvec(taps);
+            check(ldsp_synth_create_taps((unsigned)nchan, (unsigned)d, g.data(), (unsigned)g.size(), &q));
+        } else {
+            if (m < 0) throw py::value_error("Synthesizer: m must be >= 1");
+            float f = 0.0f;                                   // the C ABI's default: 1 / nchan or 0.5 / nchan
+            if (!fc.is_none()) {
+                f = fc.cast<float>();
+                if (!(f > 0.0f && f < 0.5f)) throw py::value_error("Synthesizer: Fc must lie in (0, 0.5)");
+            }
+            check(ldsp_synth_create((unsigned)nchan, (unsigned)d, (unsigned)m, f, as, &q));
+        }
+        check(ldsp_synth_get_info(q, &M, &D, &L));
+    }
+    Synthesizer(const Synthesizer&) = delete;
+    ~Synthesizer()
+    {
+        if (q) ldsp_synth_destroy(q);
+    }
+    void reset() { check(ldsp_synth_reset(q)); }
+    py::array_t<float> taps()
+    {
+        py::array_t<float> g(L);
+        check(ldsp_synth_get_taps(q, g.mutable_data()));
+        return g;
+    }
+    float get_scale()
+    {
+        float s;
+        check(ldsp_synth_get_scale(q, &s));
+        return s;
+    }
+    void set_scale(float s) { check(ldsp_synth_set_scale(q, s)); }
+    size_t tile()
+    {
+        size_t f = 0;
+        check(ldsp_debug_synth_tile(M, D, &f));
+        return f;
+    }
+    py::array_t<double> centers()
+    {
+        py::array_t<double> c(M);
+        for (unsigned k = 0; k < M; k++) c.mutable_at(k) = std::fmod((double)k / M + 0.5, 1.0) - 0.5;
+        return c;
+    }
+    size_t num_outputs(size_t K)
+    {
+        size_t n = 0;
+        check(ldsp_synth_num_outputs(q, K, &n));
+        return n;
+    }
+    void check_rows(py::ssize_t ndim, py::ssize_t rows) const
+    {
+        if (ndim != 2) throw py::value_error("Synthesizer: the input must be 2-D, [nchan, K]");
+        if (rows != (py::ssize_t)M)
+            throw py::value_error("Synthesizer: the input has " + std::to_string(rows) + " rows, nchan is " +
+                                  std::to_string(M));
+    }
+    py::object call(const py::handle& x)
+    {
+        size_t nw = 0;
+        if (is_device_tensor(x)) {
+            py::object& torch = torch_mod();
+            py::object t = py::reinterpret_borrow<py::object>(x);
+            check_rows(t.attr("dim")().cast<py::ssize_t>(), t.attr("dim")().cast<int>() == 2
+                                                                ? t.attr("size")(0).cast<py::ssize_t>()
+                                                                : 0);
+            if (!py::object(t.attr("dtype")).equal(torch.attr("complex64"))) t = t.attr("to")(torch.attr("complex64"));
+            const size_t K = t.attr("size")(1).cast<size_t>();
+            // columns one sample apart and rows that do not overlap: read in place
+            if (t.attr("stride")(1).cast<long>() != 1 || t.attr("stride")(0).cast<long>() < (long)K)
+                t = t.attr("contiguous")();
+            const size_t ld = std::max<size_t>(t.attr("stride")(0).cast<size_t>(), K);
+            py::object device = t.attr("device");
+            const int tdev = device.attr("index").cast<int>();
+            const int cur = torch.attr("cuda").attr("current_device")().cast<int>();
+            if (tdev != cur)
+                throw py::value_error("input tensor is on cuda:" + std::to_string(tdev) +
+                                      " but the current device is cuda:" + std::to_string(cur) +
+                                      " (call under torch.cuda.device(" + std::to_string(tdev) + "))");
+            void* stream = reinterpret_cast<void*>(
+                torch.attr("cuda").attr("current_stream")(device).attr("cuda_stream").cast<uintptr_t>());
+            const size_t N = num_outputs(K);
+            py::object out = dev_empty(N, true, device);
+            check(ldsp_synth_execute(q, tptr(t), ld, K, tptr(out), N, &nw, LDSP_MEM_DEVICE, stream));
+            return out;
+        }
+        carr a = carr::ensure(x);
+        if (!a) throw py::error_already_set();
+        check_rows(a.ndim(), a.ndim() == 2 ? a.shape(0) : 0);
+        const size_t K = (size_t)a.shape(1);
+        const size_t N = num_outputs(K);
+        py::array out = host_array(N, true);
+        void* zp = out.mutable_data();
+        const void* yp = a.data();
+        int rc;
+        {
+            py::gil_scoped_release rel;
+            rc = ldsp_synth_execute(q, yp, K, K, zp, N, &nw, LDSP_MEM_HOST, nullptr);
+        }
+        check(rc);
+        return out;
+    }
+};
+
 // ------------------------------------------------------------------ Spectrogram (no reference counterpart)
 // Streaming Welch periodogram (ldsp.h): complex64[n] -> float32[rows, nfft], row
 // r the mean of `average` transforms' power per bin in FFT order, plus a running
@@ -1742,6 +1859,21 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def_property_readonly("tile", &Channelizer::tile, "output columns per workgroup of the kernel")
         .def_property_readonly("centers", &Channelizer::centers, "channel centres k / nchan wrapped into [-0.5, 0.5)")
         .def("__call__", &Channelizer::call, "complex64[N] -> complex64[nchan, ncols]");
+
+    // ---- Synthesizer (beyond the reference: polyphase synthesis filter bank)
+    py::class_<Synthesizer>(m, "Synthesizer")
+        .def(py::init<int, py::object, int, py::object, float, py::object>(), py::arg("nchan"),
+             py::arg("interp") = py::none(), py::arg("m") = 6, py::arg("Fc") = py::none(), py::arg("As") = 60.0f,
+             py::arg("taps") = py::none())
+        .def("reset", &Synthesizer::reset)
+        .def("num_outputs", &Synthesizer::num_outputs, py::arg("K"), "samples a call of K columns returns")
+        .def_property_readonly("nchan", [](Synthesizer& c) { return c.M; })
+        .def_property_readonly("interp", [](Synthesizer& c) { return c.D; })
+        .def_property_readonly("taps", &Synthesizer::taps)
+        .def_property("scale", &Synthesizer::get_scale, &Synthesizer::set_scale)
+        .def_property_readonly("tile", &Synthesizer::tile, "input columns per workgroup of the kernel")
+        .def_property_readonly("centers", &Synthesizer::centers, "row centres k / nchan wrapped into [-0.5, 0.5)")
+        .def("__call__", &Synthesizer::call, "complex64[nchan, K] -> complex64[K * interp]");
 
     // ---- Spectrogram (beyond the reference: streaming Welch periodogram)
     py::class_<Spectrogram>(m, "Spectrogram")
