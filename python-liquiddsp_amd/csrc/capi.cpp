@@ -127,9 +127,14 @@ struct BufDevice {
     BufDevice(int mem, const void* x) : dev(of(mem, x)), g(dev) {}
 };
 
-static Exec make_exec(int device, int mem, void* stream, const BufDevice& bd)
+static int checked_mem(int mem)
 {
     LDSP_REQUIRE(mem == LDSP_MEM_HOST || mem == LDSP_MEM_DEVICE, "mem must be LDSP_MEM_HOST or LDSP_MEM_DEVICE");
+    return mem;
+}
+
+static Exec make_exec(int device, int mem, void* stream, const BufDevice& bd)
+{
     if (mem == LDSP_MEM_DEVICE && bd.dev != device)
         throw Error(LDSP_EINVAL, "buffer on device " + std::to_string(bd.dev) + " but the object lives on device " +
                                      std::to_string(device) + " (objects are bound to the device of their first call)");
@@ -308,25 +313,152 @@ struct Staging {
         if (bytes) LDSP_HIP(hipMemcpyAsync(y, out.p, bytes, hipMemcpyDeviceToHost, e.stream));
         LDSP_HIP(hipStreamSynchronize(e.stream));
     }
+    // A host image of `rows` rows of `row` bytes whose rows are `stride` bytes
+    // apart; the device image is dense.  Dense host images take the paths above.
+    const void* dev_in(const Exec& e, const void* x, size_t row, size_t rows, size_t stride)
+    {
+        if (!e.host || stride == row || row * rows == 0) return dev_in(e, x, row * rows);
+        in.ensure(row * rows, e.device);
+        LDSP_HIP(hipMemcpy2DAsync(in.p, row, x, stride, row, rows, hipMemcpyHostToDevice, e.stream));
+        return in.p;
+    }
+    void finish(const Exec& e, void* y, size_t row, size_t rows, size_t stride)
+    {
+        if (!e.host || stride == row || row * rows == 0) return finish(e, y, row * rows);
+        LDSP_HIP(hipMemcpy2DAsync(y, stride, out.p, row, row, rows, hipMemcpyDeviceToHost, e.stream));
+        LDSP_HIP(hipStreamSynchronize(e.stream));
+    }
 };
 
+// Streaming state on the device is ping-ponged between two buffers, so a call
+// never reads what it writes: it reads in(), writes out() and then flips.
+struct PingPong {
+    DevBuf b[2];
+    int cur = 0;
+    void* in() const { return b[cur].p; }
+    void* out() const { return b[1 - cur].p; }
+    void flip() { cur = 1 - cur; }
+    void zero(size_t bytes, int dev)
+    {
+        for (auto& d : b) zero_now(d.ensure(bytes, dev), 0, bytes);
+        cur = 0;
+    }
+};
+
+// What every object that keeps state on a device has.  An object lives on the
+// device of its first call: bind_first() runs the object's own bind(dev) -- its
+// uploads and zeroed state, on `dev`, which the caller has made current -- and
+// records the device only after bind() returned, so a bind that threw leaves
+// the object unbound and its next call binds again.
+struct DevObj {
+    int device = -1;                  // -1: not bound yet
+    hipStream_t last = nullptr;       // the stream of the last call
+    StreamMark ord;                   // cross-stream call order (ldsp_common.hpp)
+    Staging stg;
+    template <class T>
+    static int bind_first(T& o, int dev)
+    {
+        if (o.device < 0) {
+            o.bind(dev);
+            o.device = dev;
+        }
+        return o.device;
+    }
+    // everything the object has enqueued is done
+    void quiesce() const
+    {
+        if (last) LDSP_HIP(hipStreamSynchronize(last));
+        ord.sync();
+    }
+    void drain() const                // a destroy: the last call's stream only, and no error to report
+    {
+        if (last) (void)hipStreamSynchronize(last);
+    }
+    // reset-type paths: nothing before the first call; after it, `fn` runs with
+    // the object's device current and the object idle
+    template <class F>
+    void at_rest(F&& fn)
+    {
+        if (device < 0) return;
+        DeviceGuard g(device);
+        quiesce();
+        fn();
+    }
+};
+
+// One execute call on an object: validates `mem` (before any HIP call), makes
+// the device of buffer `x` current, binds the object there on its first call,
+// makes the object's device current, resolves the stream (`e`), and orders the
+// call after the object's previous one; end() marks the call's end for the
+// next.  ordered == false leaves `ord` to the caller, for objects whose calls
+// order their parts themselves.
+struct Call {
+    DevObj& o;
+    const bool ordered;
+    const BufDevice bd;
+    const DeviceGuard g;
+    const Exec e;
+    template <class T>
+    Call(T& obj, int mem, const void* x, void* stream, bool ordered_ = true)
+        : Call(obj, [&](int dev) { return DevObj::bind_first(obj, dev); }, mem, x, stream, ordered_)
+    {
+    }
+    // a call on two objects: both bind under the buffer's device and must share one (`differ`: the message if not)
+    template <class T, class U>
+    Call(T& obj, U& second, const char* differ, int mem, const void* x, void* stream, bool ordered_ = true)
+        : Call(obj,
+               [&](int dev) {
+                   DevObj::bind_first(obj, dev);
+                   DevObj::bind_first(second, dev);
+                   LDSP_REQUIRE(obj.device == second.device, differ);
+                   return obj.device;
+               },
+               mem, x, stream, ordered_)
+    {
+    }
+    void end()
+    {
+        if (ordered) o.ord.mark(e.stream);
+        o.last = e.stream;
+    }
+
+private:
+    template <class B>
+    Call(DevObj& obj, B&& bind, int mem, const void* x, void* stream, bool ordered_)
+        : o(obj), ordered(ordered_), bd(checked_mem(mem), x), g(bind(bd.dev)), e(make_exec(o.device, mem, stream, bd))
+    {
+        if (ordered) o.ord.wait(e.stream);
+    }
+};
+
+// a nested C-ABI call's failure, passed on with its message
+static void ok(int rc)
+{
+    if (rc != LDSP_OK) throw Error(rc, g_last_error);
+}
+
+// every destroy: the object's last call has finished with its buffers
+template <class T>
+static void destroy(T* q)
+{
+    if (q) q->drain();
+    delete q;
+}
+
 // ====================================================================== FIR
-struct FirObj {
+struct FirObj : DevObj {
     std::vector<float> h;
     bool cplx = false;
     float scale = 1.0f;
     int mode = LDSP_MODE_FAST;
-    int device = -1;
-    DevBuf taps_pad, taps_rev, hist[2];
+    DevBuf taps_pad, taps_rev;
+    PingPong hist;
     DevBuf fft_H, fft_tw;             // overlap-save spectrum (for fft_scale) and twiddles
     DevBuf mixbuf;                    // ldsp_nco_mix_firfilt off the fused path: the mixed samples
     float fft_scale = 0.0f;
     bool fft_ready = false;
-    int cur = 0;
-    hipStream_t last = nullptr;
-    StreamMark ord;                   // cross-stream call order (ldsp_common.hpp)
-    Staging stg;
     size_t esz() const { return cplx ? 8 : 4; }
+    size_t hist_bytes() const { return std::max<size_t>(h.size() - 1, 1) * esz(); }
     // FAST on complex data with L in [kFirFftMinTaps, 513] (fft_P() <= 512) runs
     // the overlap-save FFT kernel (HBM-bound); shorter and longer filters and
     // DIRECT use the register-blocked direct form (VALU-bound at 4 L flop / sample).
@@ -375,10 +507,8 @@ struct FirObj {
         fft_scale = scale;
         fft_ready = true;
     }
-    void ensure_device()
+    void bind(int dev)
     {
-        if (device >= 0) return;
-        const int dev = current_device();
         const int L = (int)h.size();
         std::vector<float> pad((L + 15) / 16 * 16, 0.0f), rev(L);
         for (int i = 0; i < L; i++) {
@@ -387,11 +517,7 @@ struct FirObj {
         }
         upload(taps_pad, pad, dev);
         upload(taps_rev, rev, dev);
-        for (auto& b : hist) {
-            b.ensure(std::max<size_t>(L - 1, 1) * esz(), dev);
-            zero_now(b.p, 0, std::max<size_t>(L - 1, 1) * esz());
-        }
-        device = dev;
+        hist.zero(hist_bytes(), dev);
     }
 };
 } // namespace ldsp
@@ -406,7 +532,7 @@ struct ldsp_ampmodem_s;
 namespace ldsp {
 
 // ====================================================================== resampler
-struct ResampObj {
+struct ResampObj : DevObj {
     bool cplx = true;                 // complex samples
     bool real_taps = false;           // crcf: complex samples, real taps (CResampler)
     float rate = 1.0f;
@@ -416,13 +542,10 @@ struct ResampObj {
     uint64_t phase = 0;
     float fc = 0, as = 0;
     std::vector<float> hproto, sub;   // sub: [npfb][sub_len] reversed (complex interleaved if cplx)
-    int device = -1;
-    DevBuf dsub, hist[2];
-    int cur = 0;
-    hipStream_t last = nullptr;
-    StreamMark ord;                   // cross-stream call order (ldsp_common.hpp)
-    Staging stg;
+    DevBuf dsub;
+    PingPong hist;
     size_t esz() const { return cplx ? 8 : 4; }
+    size_t hist_bytes() const { return std::max<size_t>(sub_len - 1, 1) * esz(); }
     void set_rate(float r)
     {
         LDSP_REQUIRE(r > 0, "resamp: resampling rate must be greater than zero");
@@ -449,35 +572,22 @@ struct ResampObj {
         k::resamp_plan(p, cplx, real_taps);
         return p;
     }
-    void ensure_device()
+    void bind(int dev)
     {
-        if (device >= 0) return;
-        const int dev = current_device();
         upload(dsub, sub, dev);
-        for (auto& b : hist) {
-            b.ensure(std::max<size_t>(sub_len - 1, 1) * esz(), dev);
-            zero_now(b.p, 0, std::max<size_t>(sub_len - 1, 1) * esz());
-        }
-        device = dev;
+        hist.zero(hist_bytes(), dev);
     }
 };
 
 // ====================================================================== NCO
-struct NcoObj {
+// (its state is the host's phase words: its calls mark no order, `ord` and `last` stay unset)
+struct NcoObj : DevObj {
     int type = 0;
     uint32_t theta = 0, dtheta = 0;
     float alpha = 0.1f, beta = 0.0f;
     std::vector<float> table;
-    int device = -1;
     DevBuf dtab;
-    Staging stg;
-    void ensure_device()
-    {
-        if (device >= 0) return;
-        const int dev = current_device();
-        upload(dtab, table, dev);
-        device = dev;
-    }
+    void bind(int dev) { upload(dtab, table, dev); }
 };
 
 static std::vector<float> nco_table()
@@ -497,7 +607,7 @@ static uint32_t nco_constrain(float theta)
 }
 
 // ====================================================================== IIR
-struct IirObj {
+struct IirObj : DevObj {
     bool cplx = true;
     bool sos = true;
     unsigned int nsos = 0;
@@ -505,7 +615,6 @@ struct IirObj {
     int nb = 0, na = 0, nv = 0, D = 0;
     int mode = LDSP_MODE_FAST;
     int spec_W = 0;                   // > 0: fast-decaying filter -> speculative exact chunks
-    int device = -1;
     DevBuf db, da, st32, st64, sc1, sc2, mats;
     DevBuf bmats, bsc1, bsc2, bsc3;   // blocked scan (D <= 8): matrices and scratch
     int bplan_G = 0;
@@ -525,9 +634,6 @@ struct IirObj {
     int plan_C = 0;
     long plan_nch = 0;
     int plan_G = 0;
-    hipStream_t last = nullptr;
-    StreamMark ord;                   // cross-stream call order (ldsp_common.hpp)
-    Staging stg;
     std::vector<double> A;            // D x D one-step state matrix (float64)
 
     int fsz() const { return sos ? 3 * (int)nsos : nv; }
@@ -647,10 +753,8 @@ struct IirObj {
         }
         return R;
     }
-    void ensure_device()
+    void bind(int dev)
     {
-        if (device >= 0) return;
-        const int dev = current_device();
         upload(db, b, dev);
         upload(da, a, dev);
         st32.ensure(sizeof(float) * 2 * std::max(fsz(), 1), dev);
@@ -664,7 +768,6 @@ struct IirObj {
             upload(mtab, mf.tables, dev);
         }
         state_at = kSt32;
-        device = dev;
     }
     k::IirDesc desc() const
     {
@@ -862,10 +965,9 @@ struct IirObj {
 };
 
 // ====================================================================== AGC
-struct AgcObj {
+struct AgcObj : DevObj {
     k::AgcState h{};                  // host mirror
     float bandwidth = 0.01f;
-    int device = -1;
     DevBuf dst, status;
     // Per-call scratch in two slots (call parity) and the input history the
     // speculative warm-ups read (the last hist_len samples before the call, in
@@ -877,11 +979,9 @@ struct AgcObj {
     uint64_t ncall = 0;
     bool dev_newer = false;           // device state advanced past the mirror
     bool upload_pending = true;
-    hipStream_t last = nullptr;
     // Cross-stream order (ldsp_common.hpp): ord = back halves (the true
     // state), front = front halves (history), slot[s] = scratch slot s free.
-    StreamMark ord, front, slot[2];
-    Staging stg;
+    StreamMark front, slot[2];
     int tsa_perturb = 0;              // ldsp_debug_agc_tsa_perturb (test hook)
     int perturb = 0;                  // ldsp_debug_agc_perturb (test hook, chunk-parallel calls)
     int rounds_force = -1;            // ldsp_debug_agc_rounds (test hook; -1: the default)
@@ -909,12 +1009,9 @@ struct AgcObj {
         dev_newer = false;
     }
     void modified() { upload_pending = true; }
-    void ensure_device()
+    void bind(int dev)
     {
-        if (device >= 0) return;
-        const int dev = current_device();
         dst.ensure(sizeof(k::AgcState), dev);
-        device = dev;
         upload_pending = true;
     }
 };
@@ -997,7 +1094,7 @@ static ErrFlags& err_flags()
 static constexpr unsigned long long kWalkWaitTicks = 100000000ull;   // 1 s of s_memrealtime (100 MHz)
 // ldsp_debug_walk_early: -1 default (early hand-off on), 0 / 1 forced
 static std::atomic<int> g_walk_early{-1};
-struct AmpObj {
+struct AmpObj : DevObj {
     AmpLive live;
     uint32_t* herr = nullptr;             // host-mapped walker timeout flag (ErrFlags)
     float mod_index = 0.75f;
@@ -1006,11 +1103,11 @@ struct AmpObj {
     unsigned int m = 25;
     std::vector<float> lp, dc, hq, table;     // hq: the usb / lsb Hilbert transform's 2m quadrature taps
     k::AmpState st{};
-    int device = -1;
-    DevBuf dlp, ddc, dtab, dst, lph[2], dch[2];
+    DevBuf dlp, ddc, dtab, dst;
+    PingPong lph, dch;                        // carrier lowpass and DC blocker histories (flipped together)
     // usb / lsb: Hilbert taps, its input history (4m - 1 samples, ping-pong) and per-slot v1 scratch
-    DevBuf dhq, hbh[2], v1[2];
-    int hcur = 0;
+    DevBuf dhq, v1[2];
+    PingPong hbh;
     // Per-call scratch in two slots (call parity) and the delay-line history in
     // three (call index mod 3), so that call k's front half (lowpass, history,
     // candidates) can run while call k-1's walker still reads its own slot.
@@ -1019,15 +1116,12 @@ struct AmpObj {
     uint32_t wexp = 0;                    // launches issued that write the PLL state (AmpState::wepoch)
     size_t last_pll_n = 0;                // samples of the last call's PLL launch
     const void* last_stats = nullptr;     // walker counters of the last parallel call (in its scratch slot)
-    int cur = 0;
     bool dev_newer = false;
-    hipStream_t last = nullptr;
     // Cross-stream order (ldsp_common.hpp): `front` = end of a call's front half
     // (lowpass + delay histories, candidate guess state), `ord` = end of a call's
     // walk (true PLL state), `post` = end of its DC blocker (history),
     // `slot[i]` = end of the last call that used scratch slot i.
-    StreamMark front, ord, post, slot[2];
-    Staging stg;
+    StreamMark front, post, slot[2];
     void reset_host()
     {
         st.theta = 0;
@@ -1046,10 +1140,8 @@ struct AmpObj {
         front.sync();
         for (auto& sm : slot) sm.sync();
     }
-    void ensure_device()
+    void bind(int dev)
     {
-        if (device >= 0) return;
-        const int dev = current_device();
         std::vector<float> lr(lp.rbegin(), lp.rend()), dr(dc.rbegin(), dc.rend());
         upload(dlp, lr, dev);
         upload(ddc, dr, dev);
@@ -1063,24 +1155,13 @@ struct AmpObj {
         if (!st.wait_ticks) st.wait_ticks = kWalkWaitTicks;
         LDSP_HIP(hipMemcpy(dst.p, &st, sizeof(st), hipMemcpyHostToDevice));
         live.set(dev);
-        for (int i = 0; i < 2; i++) {
-            lph[i].ensure((2 * m) * 8, dev);
-            zero_now(lph[i].p, 0, (2 * m) * 8);
-            dch[i].ensure((2 * m) * 4, dev);
-            zero_now(dch[i].p, 0, (2 * m) * 4);
-        }
-        for (auto& b : dlh) {
-            b.ensure(m * 8, dev);
-            zero_now(b.p, 0, m * 8);
-        }
+        lph.zero((2 * m) * 8, dev);
+        dch.zero((2 * m) * 4, dev);
+        for (auto& b : dlh) zero_now(b.ensure(m * 8, dev), 0, m * 8);
         if (!hq.empty()) {
             upload(dhq, hq, dev);
-            for (auto& b : hbh) {
-                b.ensure((4 * m - 1) * 8, dev);
-                zero_now(b.p, 0, (4 * m - 1) * 8);
-            }
+            hbh.zero((4 * m - 1) * 8, dev);
         }
-        device = dev;
     }
     AmpObj() = default;
     AmpObj(const AmpObj&) = delete;
@@ -1103,147 +1184,152 @@ struct ldsp_ampmodem_s : ldsp::AmpObj {};
 // == re(v1)) followed by an owned SOS IIR DC blocker instead of the FIR one.
 struct ldsp_bcastam_s : ldsp::AmpObj {
     ldsp_iirfilt_t dcb = nullptr;
+    ~ldsp_bcastam_s() { ldsp_iirfilt_destroy(dcb); }
 };
 
-// Streaming state of the per-sample kernels lives on the device, ping-ponged
-// between two buffers so a call never reads what it writes.
-struct ldsp_freqdem_s {
+struct ldsp_freqdem_s : ldsp::DevObj {
     float kf = 0.0f, ref = 0.0f;
-    int device = -1, cur = 0;
-    ldsp::DevBuf prev[2];
-    hipStream_t last = nullptr;
-    ldsp::StreamMark ord;                   // cross-stream call order (ldsp_common.hpp)
-    ldsp::Staging stg;
+    ldsp::PingPong prev;                    // the last input sample
+    void bind(int dev) { prev.zero(8, dev); }
 };
 
 // FMStereo (demod.hpp:4-85): freqdem(4) + mixer loop + two TF de-emphasis
 // filters (exact) + two resamp_rrrf_create_default resamplers.
-struct ldsp_fmstereo_s {
+struct ldsp_fmstereo_s : ldsp::DevObj {
     float iq_rate = 0, pcm_rate = 0;
     ldsp_freqdem_t dem = nullptr;
     ldsp_iirfilt_t emph[2] = {nullptr, nullptr};
     ldsp_resamp_t aud[2] = {nullptr, nullptr};
     std::vector<float> table;
     ldsp::k::FmState st{};
-    int device = -1;
     ldsp::DevBuf dst, dtab, sbuf, lr[2], le[2], out[2];
-    hipStream_t last = nullptr;
-    ldsp::StreamMark ord;                  // cross-stream call order (ldsp_common.hpp)
-    ldsp::Staging stg;
+    void bind(int dev)
+    {
+        dst.ensure(sizeof(st), dev);
+        LDSP_HIP(hipMemcpy(dst.p, &st, sizeof(st), hipMemcpyHostToDevice));
+        ldsp::upload(dtab, table, dev);
+    }
+    ~ldsp_fmstereo_s()
+    {
+        ldsp_freqdem_destroy(dem);
+        for (int c = 0; c < 2; c++) {
+            ldsp_iirfilt_destroy(emph[c]);
+            ldsp_resamp_destroy(aud[c]);
+        }
+    }
 };
 
-struct ldsp_delay_s {
+struct ldsp_delay_s : ldsp::DevObj {
     unsigned int nd = 1;
-    int device = -1, cr = 0, cc = 0;
-    ldsp::DevBuf hr[2], hc[2];     // real / complex lines of nd + 1 samples
-    hipStream_t last = nullptr;
-    ldsp::StreamMark ord;                  // cross-stream call order (ldsp_common.hpp)
-    ldsp::Staging stg;
-    void zero()
+    ldsp::PingPong hr, hc;         // real / complex lines of nd + 1 samples
+    void zero(int dev)
     {
-        for (int i = 0; i < 2; i++) {
-            ldsp::zero_now(hr[i].ensure((nd + 1) * 4, device), 0, (nd + 1) * 4);
-            ldsp::zero_now(hc[i].ensure((nd + 1) * 8, device), 0, (nd + 1) * 8);
-        }
-        cr = cc = 0;
+        hr.zero((nd + 1) * 4, dev);
+        hc.zero((nd + 1) * 8, dev);
     }
+    void bind(int dev) { zero(dev); }
 };
 
 // firhilbf (SSBDemod, HilbertTransform): the 2m quadrature taps and, on the
 // device, the last H input samples in the input's layout, ping-ponged.
-struct ldsp_firhilb_s {
+struct ldsp_firhilb_s : ldsp::DevObj {
     unsigned int m = 0;
     int op = 0;
     std::vector<float> hq;
-    int device = -1, cur = 0;
-    ldsp::DevBuf dhq, hist[2];
-    hipStream_t last = nullptr;
-    ldsp::StreamMark ord;                  // cross-stream call order (ldsp_common.hpp)
-    ldsp::Staging stg, stg1;               // stg1: the second output of a host-memory C2R call
+    ldsp::DevBuf dhq;
+    ldsp::PingPong hist;
+    ldsp::Staging stg1;                    // the second output of a host-memory C2R call
     size_t in_size() const { return op == LDSP_HILB_C2R || op == LDSP_HILB_INTERP ? 8 : 4; }
     size_t hist_bytes() const { return (size_t)(op == LDSP_HILB_INTERP ? 2 * m - 1 : 4 * m - 1) * in_size(); }
-    void zero()
+    void bind(int dev)
     {
-        for (auto& b : hist) ldsp::zero_now(b.ensure(hist_bytes(), device), 0, hist_bytes());
-        cur = 0;
+        std::vector<float> pad(hq);
+        pad.resize(pad.size() + ldsp::k::kHilbTapPad, 0.0f);
+        ldsp::upload(dhq, pad, dev);
+        hist.zero(hist_bytes(), dev);
     }
 };
 
-// Channelizer (polyphase analysis bank): the prototype, the host-side stream
-// position (samples seen; skip and the output parity follow from it), and on
-// the device the padded taps, the twiddle table and the last P M - 1 input
-// samples, ping-ponged.
-struct ldsp_chan_s {
-    unsigned int M = 0, D = 0, P = 0;
+// The two polyphase banks: the prototype, the host-side stream position, and
+// on the device the taps padded to kChanMaxP M, the twiddle table
+// exp(2 pi i j / M), j < M, as (re, im) pairs (double, rounded once) and the
+// input history, ping-ponged.
+struct BankObj : ldsp::DevObj {
+    unsigned int M = 0, D = 0;
+    unsigned int R = 0;                    // taps per branch: the Channelizer's P, the Synthesizer's Q
     std::vector<float> h;
     float scale = 1.0f;
-    uint64_t seen = 0;                     // input samples since create / reset
-    int device = -1, cur = 0;
-    ldsp::DevBuf dtaps, dtw, hist[2];
-    hipStream_t last = nullptr;
-    ldsp::StreamMark ord;                  // cross-stream call order (ldsp_common.hpp)
-    ldsp::Staging stg;
-    size_t hist_bytes() const { return ((size_t)P * M - 1) * 8; }
+    uint64_t seen = 0;                     // input samples (Synthesizer: columns) since create / reset
+    size_t hist_bytes = 0;
+    ldsp::DevBuf dtaps, dtw;
+    ldsp::PingPong hist;
+    void bind(int dev)
+    {
+        std::vector<float> pad(h);
+        pad.resize((size_t)ldsp::k::kChanMaxP * M, 0.0f);
+        ldsp::upload(dtaps, pad, dev);
+        std::vector<float> tw(2 * (size_t)M);
+        for (unsigned j = 0; j < M; j++) {
+            const double a = 2.0 * M_PI * (double)j / (double)M;
+            tw[2 * j] = (float)cos(a);
+            tw[2 * j + 1] = (float)sin(a);
+        }
+        ldsp::upload(dtw, tw, dev);
+        hist.zero(hist_bytes, dev);
+    }
+};
+
+// Channelizer (polyphase analysis bank): skip and the output parity follow from
+// the samples seen; the history is the last P M - 1 input samples.
+struct ldsp_chan_s : BankObj {
     size_t skip() const { return (size_t)((D - seen % D) % D); }
     size_t num_outputs(size_t n) const { return n > skip() ? (n - skip() + D - 1) / D : 0; }
     int parity() const { return (int)(((seen + D - 1) / D) & 1); }   // of the next output's absolute index
-    void zero()
-    {
-        for (auto& b : hist) ldsp::zero_now(b.ensure(hist_bytes(), device), 0, hist_bytes());
-        cur = 0;
-    }
 };
 
-// Synthesizer (polyphase synthesis bank): the prototype, the host-side column
-// count (the D = M / 2 sign's parity follows from it), and on the device the
-// padded taps, the twiddle table and the last Q - 1 input columns as
-// [M][Q - 1], ping-ponged.
-struct ldsp_synth_s {
-    unsigned int M = 0, D = 0, Q = 0;
-    std::vector<float> g;
-    float scale = 1.0f;
-    uint64_t seen = 0;                     // input columns since create / reset
-    int device = -1, cur = 0;
-    ldsp::DevBuf dtaps, dtw, hist[2];
-    hipStream_t last = nullptr;
-    ldsp::StreamMark ord;
-    ldsp::Staging stg;
-    size_t hist_bytes() const { return std::max<size_t>((size_t)M * (Q - 1), 1) * 8; }
-    void zero()
-    {
-        for (auto& b : hist) ldsp::zero_now(b.ensure(hist_bytes(), device), 0, hist_bytes());
-        cur = 0;
-    }
-};
+// Synthesizer (polyphase synthesis bank): the D = M / 2 sign's parity follows
+// from the columns seen; the history is the last Q - 1 input columns as [M][Q - 1].
+struct ldsp_synth_s : BankObj {};
 
 // Spectrogram (streaming Welch periodogram): the window, the host-side counts
 // (samples since reset, transforms since clear; the schedule follows from
 // them), and on the device the padded window, the twiddle table, the last
 // W - 1 input samples and the unfinished row's sum (both ping-ponged), the
 // float64 accumulator and the per-workgroup sums it is fed from.
-struct ldsp_spgram_s {
+struct ldsp_spgram_s : ldsp::DevObj {
     unsigned int N = 0, W = 0, d = 0, A = 0;
     std::vector<float> w;
     uint64_t seen = 0;                     // input samples since create / reset
     uint64_t nacc = 0;                     // transforms since create / reset / clear
-    int device = -1, cur = 0, ccur = 0, rcur = 0;
     // carry: the unfinished row's sum (blocked averages: the unfinished block's);
     // blk, rcarry: a blocked average's block sums and its unfinished row's
-    ldsp::DevBuf dwin, dtw, hist[2], carry[2], rcarry[2], dpsd, part, blk;
-    hipStream_t last = nullptr;
-    ldsp::StreamMark ord;
-    ldsp::Staging stg;
+    ldsp::DevBuf dwin, dtw, dpsd, part, blk;
+    ldsp::PingPong hist, carry, rcarry;
     size_t hist_bytes() const { return std::max<size_t>((size_t)W - 1, 1) * 8; }
     size_t transforms(size_t n) const { return (size_t)((seen + n) / d - seen / d); }
     size_t rows(size_t n) const { return (size_t)((seen + n) / d / A - seen / d / A); }
-    void zero_stream()
+    void zero_stream(int dev)
     {
-        for (auto& b : hist) ldsp::zero_now(b.ensure(hist_bytes(), device), 0, hist_bytes());
-        for (auto& b : carry) ldsp::zero_now(b.ensure((size_t)N * 4, device), 0, (size_t)N * 4);
-        for (auto& b : rcarry) ldsp::zero_now(b.ensure((size_t)N * 4, device), 0, (size_t)N * 4);
-        cur = ccur = rcur = 0;
+        hist.zero(hist_bytes(), dev);
+        carry.zero((size_t)N * 4, dev);
+        rcarry.zero((size_t)N * 4, dev);
     }
-    void zero_psd() { ldsp::zero_now(dpsd.ensure((size_t)N * 8, device), 0, (size_t)N * 8); }
+    void zero_psd(int dev) { ldsp::zero_now(dpsd.ensure((size_t)N * 8, dev), 0, (size_t)N * 8); }
+    void bind(int dev)
+    {
+        std::vector<float> pad(w);
+        pad.resize(N, 0.0f);
+        ldsp::upload(dwin, pad, dev);
+        std::vector<float> tw(2 * (size_t)N);             // exp(-2 pi i j / N): double, rounded once
+        for (unsigned j = 0; j < N; j++) {
+            const double a = -2.0 * M_PI * (double)j / (double)N;
+            tw[2 * j] = (float)cos(a);
+            tw[2 * j + 1] = (float)sin(a);
+        }
+        ldsp::upload(dtw, tw, dev);
+        zero_stream(dev);
+        zero_psd(dev);
+    }
 };
 
 using namespace ldsp;
@@ -1493,13 +1579,7 @@ int ldsp_firfilt_create_dc_blocker(unsigned int m, float as, int cplx, ldsp_firf
     });
 }
 
-int ldsp_firfilt_destroy(ldsp_firfilt_t q)
-{
-    return guard([&] {
-        if (q && q->last) (void)hipStreamSynchronize(q->last);
-        delete q;
-    });
-}
+int ldsp_firfilt_destroy(ldsp_firfilt_t q) { return guard([&] { destroy(q); }); }
 
 int ldsp_firfilt_reset(ldsp_firfilt_t q)
 {
@@ -1507,8 +1587,7 @@ int ldsp_firfilt_reset(ldsp_firfilt_t q)
         NONNULL(q);
         if (q->device < 0) return;
         DeviceGuard g(q->device);
-        const size_t bytes = std::max<size_t>(q->h.size() - 1, 1) * q->esz();
-        for (auto& b : q->hist) LDSP_HIP(hipMemsetAsync(b.p, 0, bytes, q->last));
+        for (auto& b : q->hist.b) LDSP_HIP(hipMemsetAsync(b.p, 0, q->hist_bytes(), q->last));
         q->ord.mark(q->last);              // a call on another stream waits for the zeroing
     });
 }
@@ -1563,8 +1642,8 @@ int ldsp_firfilt_freqresponse(ldsp_firfilt_t q, float f, float* re, float* im)
 static void fir_dispatch(ldsp_firfilt_s* q, const void* dx, size_t n, void* dy, hipStream_t s, const k::NcoFuse* fuse)
 {
     const int L = (int)q->h.size();
-    void* hin = q->hist[q->cur].p;
-    void* hout = q->hist[1 - q->cur].p;
+    void* hin = q->hist.in();
+    void* hout = q->hist.out();
     if (L <= 1 && n == 0) return;
     const FirObj::Kernel kern = q->kernel_for(n);
     if (kern == FirObj::kExact)
@@ -1577,7 +1656,7 @@ static void fir_dispatch(ldsp_firfilt_s* q, const void* dx, size_t n, void* dy, 
         k::fir_fft(dx, hin, hout, n, L, q->fft_P(), q->fft_H.p, q->fft_tw.p, dy, s, fuse);
     } else
         k::fir_fast(q->cplx, dx, hin, hout, n, q->taps_pad.as<float>(), L, q->scale, dy, s);
-    if (L > 1) q->cur = 1 - q->cur;
+    if (L > 1) q->hist.flip();
 }
 
 int ldsp_firfilt_execute(ldsp_firfilt_t q, const void* x, size_t n, void* y, int mem, void* stream)
@@ -1586,17 +1665,13 @@ int ldsp_firfilt_execute(ldsp_firfilt_t q, const void* x, size_t n, void* y, int
     return guard([&] {
         NONNULL(q);
         LDSP_REQUIRE(n == 0 || (x && y), "firfilt_execute: NULL buffer");
-        const BufDevice bd(mem, x);
-        q->ensure_device();
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
-        q->ord.wait(e.stream);
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
         const size_t bytes = n * q->esz();
         const void* dx = q->stg.dev_in(e, x, bytes);
         void* dy = q->stg.dev_out(e, y, bytes);
         fir_dispatch(q, dx, n, dy, e.stream, nullptr);
-        q->ord.mark(e.stream);
-        q->last = e.stream;
+        call.end();
         q->stg.finish(e, y, bytes);
     });
 }
@@ -1646,13 +1721,7 @@ int ldsp_resamp_create_default(float rate, int kind, ldsp_resamp_t* q)
     return ldsp_resamp_create(rate, 7, 0.25f, 60.0f, 256, kind, q);
 }
 
-int ldsp_resamp_destroy(ldsp_resamp_t q)
-{
-    return guard([&] {
-        if (q && q->last) (void)hipStreamSynchronize(q->last);
-        delete q;
-    });
-}
+int ldsp_resamp_destroy(ldsp_resamp_t q) { return guard([&] { destroy(q); }); }
 
 int ldsp_resamp_reset(ldsp_resamp_t q)
 {
@@ -1661,8 +1730,7 @@ int ldsp_resamp_reset(ldsp_resamp_t q)
         q->phase = 0;
         if (q->device < 0) return;
         DeviceGuard g(q->device);
-        const size_t bytes = std::max<size_t>(q->sub_len - 1, 1) * q->esz();
-        for (auto& b : q->hist) LDSP_HIP(hipMemsetAsync(b.p, 0, bytes, q->last));
+        for (auto& b : q->hist.b) LDSP_HIP(hipMemsetAsync(b.p, 0, q->hist_bytes(), q->last));
         q->ord.mark(q->last);              // a call on another stream waits for the zeroing
     });
 }
@@ -1706,22 +1774,17 @@ int ldsp_resamp_execute(ldsp_resamp_t q, const void* x, size_t n, void* y, size_
         if (K > cap) throw Error(LDSP_ERANGE, "resamp_execute: output capacity too small");
         LDSP_REQUIRE(n == 0 || x, "resamp_execute: NULL input");
         LDSP_REQUIRE(K == 0 || y, "resamp_execute: NULL output");
-        const BufDevice bd(mem, x);
-        q->ensure_device();
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
-        q->ord.wait(e.stream);
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
         const void* dx = q->stg.dev_in(e, x, n * q->esz());
         void* dy = q->stg.dev_out(e, y, K * q->esz());
         if (n > 0) {
             const k::ResampPlan p = q->plan(n);
-            k::resamp(q->cplx, q->real_taps, dx, q->hist[q->cur].p, q->hist[1 - q->cur].p, n, q->dsub.as<float>(), p, dy,
-                      e.stream);
-            if (q->sub_len > 1) q->cur = 1 - q->cur;
+            k::resamp(q->cplx, q->real_taps, dx, q->hist.in(), q->hist.out(), n, q->dsub.as<float>(), p, dy, e.stream);
+            if (q->sub_len > 1) q->hist.flip();
             q->phase = (uint64_t)((long long)q->phase + (long long)K * q->step - (long long)n * (1LL << 24));
         }
-        q->ord.mark(e.stream);
-        q->last = e.stream;
+        call.end();
         q->stg.finish(e, y, K * q->esz());
     });
 }
@@ -1740,7 +1803,7 @@ int ldsp_nco_create(int type, ldsp_nco_t* q)
         *q = o;
     });
 }
-int ldsp_nco_destroy(ldsp_nco_t q) { return guard([&] { delete q; }); }
+int ldsp_nco_destroy(ldsp_nco_t q) { return guard([&] { destroy(q); }); }
 int ldsp_nco_reset(ldsp_nco_t q) { return guard([&] { NONNULL(q); q->theta = 0; q->dtheta = 0; }); }
 int ldsp_nco_set_frequency(ldsp_nco_t q, float f) { return guard([&] { NONNULL(q); q->dtheta = nco_constrain(f); }); }
 int ldsp_nco_adjust_frequency(ldsp_nco_t q, float df)
@@ -1801,10 +1864,8 @@ int ldsp_nco_mix(ldsp_nco_t q, const void* x, size_t n, void* y, int down, int m
     return guard([&] {
         NONNULL(q);
         LDSP_REQUIRE(n == 0 || (x && y), "nco_mix: NULL buffer");
-        const BufDevice bd(mem, x);
-        q->ensure_device();
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
+        Call call(*q, mem, x, stream, false);     // no device state to order: the phase advances on the host
+        const Exec& e = call.e;
         const void* dx = q->stg.dev_in(e, x, n * 8);
         void* dy = q->stg.dev_out(e, y, n * 8);
         k::nco_mix(dx, dy, n, q->theta, q->dtheta, q->dtab.as<float>(), down != 0, q->type, e.stream);
@@ -1823,13 +1884,8 @@ int ldsp_nco_mix_firfilt(ldsp_nco_t nco, ldsp_firfilt_t q, const void* x, size_t
         NONNULL(q);
         LDSP_REQUIRE(q->cplx, "nco_mix_firfilt: the filter must be complex (firfilt_crcf / ComplexFIRFilter)");
         LDSP_REQUIRE(n == 0 || (x && y), "nco_mix_firfilt: NULL buffer");
-        const BufDevice bd(mem, x);
-        q->ensure_device();
-        nco->ensure_device();
-        LDSP_REQUIRE(nco->device == q->device, "nco_mix_firfilt: the NCO and the filter live on different devices");
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
-        q->ord.wait(e.stream);
+        Call call(*q, *nco, "nco_mix_firfilt: the NCO and the filter live on different devices", mem, x, stream);
+        const Exec& e = call.e;
         const size_t bytes = n * 8;
         const void* dx = q->stg.dev_in(e, x, bytes);
         void* dy = q->stg.dev_out(e, y, bytes);
@@ -1845,8 +1901,7 @@ int ldsp_nco_mix_firfilt(ldsp_nco_t nco, ldsp_firfilt_t q, const void* x, size_t
             fir_dispatch(q, dx, 0, dy, e.stream, nullptr);
         }
         nco->theta += (uint32_t)((uint64_t)n * nco->dtheta);
-        q->ord.mark(e.stream);
-        q->last = e.stream;
+        call.end();
         q->stg.finish(e, y, bytes);
     });
 }
@@ -1922,13 +1977,7 @@ int ldsp_iirfilt_create_prototype(int ftype, int btype, unsigned int order, floa
     });
 }
 
-int ldsp_iirfilt_destroy(ldsp_iirfilt_t q)
-{
-    return guard([&] {
-        if (q && q->last) (void)hipStreamSynchronize(q->last);
-        delete q;
-    });
-}
+int ldsp_iirfilt_destroy(ldsp_iirfilt_t q) { return guard([&] { destroy(q); }); }
 
 int ldsp_iirfilt_reset(ldsp_iirfilt_t q)
 {
@@ -2107,11 +2156,8 @@ static int iirfilt_execute(ldsp_iirfilt_t q, const void* x, size_t n, void* y, i
         NONNULL(q);
         LDSP_REQUIRE(n == 0 || (x && y), "iirfilt_execute: NULL buffer");
         LDSP_REQUIRE(!iq16 || q->cplx, "iirfilt_execute_iq16: the filter is real; int16 IQ input needs a complex one");
-        const BufDevice bd(mem, x);
-        q->ensure_device();
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
-        q->ord.wait(e.stream);
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
         const size_t bytes = n * (q->cplx ? 8 : 4);
         const void* dx = q->stg.dev_in(e, x, iq16 ? n * 4 : bytes);
         void* dy = q->stg.dev_out(e, y, bytes);
@@ -2162,8 +2208,7 @@ static int iirfilt_execute(ldsp_iirfilt_t q, const void* x, size_t n, void* y, i
             }
             }
         }
-        q->ord.mark(e.stream);
-        q->last = e.stream;
+        call.end();
         q->stg.finish(e, y, bytes);
     });
 }
@@ -2196,20 +2241,14 @@ int ldsp_iirfilt_resamp_execute(ldsp_iirfilt_t q, ldsp_resamp_t rs, const void* 
         if (K > cap) throw Error(LDSP_ERANGE, "iirfilt_resamp_execute: output capacity too small");
         LDSP_REQUIRE(n == 0 || x, "iirfilt_resamp_execute: NULL input");
         LDSP_REQUIRE(K == 0 || y, "iirfilt_resamp_execute: NULL output");
-        const BufDevice bd(mem, x);
-        q->ensure_device();
-        rs->ensure_device();
-        LDSP_REQUIRE(q->device == rs->device, "iirfilt_resamp_execute: the filter and the resampler live on different "
-                                              "devices");
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
+        // (each path below orders both objects itself: the two calls do, the fused pass waits for and marks both)
+        Call call(*q, *rs, "iirfilt_resamp_execute: the filter and the resampler live on different devices", mem, x,
+               stream, false);
+        const Exec& e = call.e;
         const size_t es = q->cplx ? 8 : 4;
         const bool fuse = n > 0 && q->path_for(n) == IirObj::kModal && rs->sub_len >= 2 &&
                           rs->sub_len - 1 <= 1024u;
         if (!fuse) {
-            auto ok = [](int rc) {
-                if (rc != LDSP_OK) throw Error(rc, ldsp_last_error());
-            };
             if (e.host) {
                 // the hand-over in page-locked memory when the pool has it (the two
                 // calls then DMA it directly), pageable otherwise; the caller's stream
@@ -2252,14 +2291,14 @@ int ldsp_iirfilt_resamp_execute(ldsp_iirfilt_t q, ldsp_resamp_t rs, const void* 
         f.side = (float*)q->rsside.ensure(k::iir_resamp_side_bytes(n, (int)rs->sub_len, q->cplx), q->device);
         f.y = (float*)dy;
         k::iir_modal_resamp(q->cplx, q->mf.cf, dx, n, q->mst.as<double>(), q->mstb.as<double>(), p, f,
-                            rs->hist[rs->cur].p, rs->hist[1 - rs->cur].p, e.stream);
+                            rs->hist.in(), rs->hist.out(), e.stream);
         std::swap(q->mst.p, q->mstb.p);
         std::swap(q->mst.cap, q->mstb.cap);
-        rs->cur = 1 - rs->cur;
+        rs->hist.flip();
         rs->phase = (uint64_t)((long long)rs->phase + (long long)K * rs->step - (long long)n * (1LL << 24));
         q->ord.mark(e.stream);
         rs->ord.mark(e.stream);
-        q->last = e.stream;
+        call.end();
         rs->last = e.stream;
         rs->stg.finish(e, y, K * es);
     });
@@ -2275,13 +2314,7 @@ int ldsp_agc_create(ldsp_agc_t* q)
         *q = o;
     });
 }
-int ldsp_agc_destroy(ldsp_agc_t q)
-{
-    return guard([&] {
-        if (q && q->last) (void)hipStreamSynchronize(q->last);
-        delete q;
-    });
-}
+int ldsp_agc_destroy(ldsp_agc_t q) { return guard([&] { destroy(q); }); }
 
 // agc_crcf_reset: g = 1, y2' = 1, unlock, squelch ENABLED unless disabled
 int ldsp_agc_reset(ldsp_agc_t q)
@@ -2466,10 +2499,8 @@ int ldsp_agc_execute(ldsp_agc_t q, const void* x, size_t n, void* y, uint8_t* st
     return guard([&] {
         NONNULL(q);
         LDSP_REQUIRE(n == 0 || (x && y), "agc_execute: NULL buffer");
-        const BufDevice bd(mem, x);
-        q->ensure_device();
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
+        Call call(*q, mem, x, stream, false);     // the halves order themselves: front / slot[] here, ord between them
+        const Exec& e = call.e;
         const int sl = (int)(q->ncall & 1), h3 = (int)(q->ncall % 3);
         q->slot[sl].wait(e.stream);
         q->front.wait(e.stream);
@@ -2560,12 +2591,28 @@ int ldsp_agc_execute(ldsp_agc_t q, const void* x, size_t n, void* y, uint8_t* st
         q->ord.mark(e.stream);
         q->slot[sl].mark(e.stream);
         q->ncall++;
-        q->last = e.stream;
+        call.end();
         if (status && n > 0) {
             LDSP_HIP(hipMemcpyAsync(status, dstat, n, hipMemcpyDeviceToHost, e.stream));
             LDSP_HIP(hipStreamSynchronize(e.stream));
         }
         q->stg.finish(e, y, n * 8);
+    });
+}
+
+int ldsp_debug_agc_dispatch(ldsp_agc_t q, size_t n, int* path, int* W, int* Wa, int* C, long* hist_len,
+                            long* hist_valid, int* spec)
+{
+    return guard([&] {
+        NONNULL(q);
+        const AgcChoice ch = agc_choice(q, n);
+        if (path) *path = ch.path;
+        if (W) *W = ch.W;
+        if (Wa) *Wa = ch.Wa;
+        if (C) *C = ch.C;
+        if (hist_len) *hist_len = ch.hist_len;
+        if (hist_valid) *hist_valid = ch.hist_len == q->hist_len ? q->hist_valid : 0;
+        if (spec) *spec = ch.spec ? 1 : 0;
     });
 }
 
@@ -2588,13 +2635,7 @@ int ldsp_ampmodem_create(float mod_index, int type, int suppressed_carrier, ldsp
         *q = o.release();
     });
 }
-int ldsp_ampmodem_destroy(ldsp_ampmodem_t q)
-{
-    return guard([&] {
-        if (q && q->last) (void)hipStreamSynchronize(q->last);
-        delete q;
-    });
-}
+int ldsp_ampmodem_destroy(ldsp_ampmodem_t q) { return guard([&] { destroy(q); }); }
 static void amp_reset(AmpObj* q)
 {
     q->reset_host();
@@ -2606,15 +2647,12 @@ static void amp_reset(AmpObj* q)
     q->st.werr = 0;
     if (q->herr) __atomic_store_n(q->herr, 0u, __ATOMIC_RELEASE);
     LDSP_HIP(hipMemcpy(q->dst.p, &q->st, sizeof(q->st), hipMemcpyHostToDevice));
-    for (int i = 0; i < 2; i++) {
-        for (DevBuf* b : {&q->lph[i], &q->dch[i]})
-            if (b->p) zero_now(b->p, 0, b->cap);
-    }
+    for (PingPong* h : {&q->lph, &q->dch, &q->hbh})
+        for (auto& b : h->b)
+            if (b.p) zero_now(b.p, 0, b.cap);
     for (auto& b : q->dlh)
         if (b.p) zero_now(b.p, 0, b.cap);
-    for (auto& b : q->hbh)
-        if (b.p) zero_now(b.p, 0, b.cap);
-    q->hcur = 0;
+    q->hbh.cur = 0;
 }
 int ldsp_ampmodem_reset(ldsp_ampmodem_t q)
 {
@@ -2775,7 +2813,7 @@ static float* amp_pll_stage(AmpObj* q, const Exec& e, const void* dx, size_t n, 
     if (costas) q->ord.wait(e.stream);
     if (!mbuf) mbuf = (float*)q->mb[sl].ensure(n * 4, q->device);
     void* x0 = q->x0[sl].ensure(n * 8, q->device);
-    k::fir_exact(true, dx, q->lph[q->cur].p, q->lph[1 - q->cur].p, n, q->dlp.as<float>(), L, 1.0f, x0, e.stream);
+    k::fir_exact(true, dx, q->lph.in(), q->lph.out(), n, q->dlp.as<float>(), L, 1.0f, x0, e.stream);
     k::PllCall c;
     c.x0 = x0;
     c.x = dx;
@@ -2837,7 +2875,8 @@ static void amp_call_end(AmpObj* q, const Exec& e)
 {
     q->slot[q->ncall & 1].mark(e.stream);
     q->ncall++;
-    q->cur = 1 - q->cur;
+    q->lph.flip();
+    q->dch.flip();
     q->dev_newer = true;
 }
 
@@ -2852,10 +2891,10 @@ static void amp_ssb(AmpObj* q, const Exec& e, const void* dx, size_t n, float* d
     const int M = (int)q->m, H = 4 * M - 1, usb = q->type == 1 ? 1 : 0;
     if (q->suppressed) {
         q->post.wait(e.stream);
-        k::ssb_c2r(dx, q->hbh[q->hcur].p, n, q->dhq.as<float>(), M, usb, q->mod_index, dy, e.stream);
-        k::delay_hist(dx, q->hbh[q->hcur].p, q->hbh[1 - q->hcur].p, n, H, e.stream);
+        k::ssb_c2r(dx, q->hbh.in(), n, q->dhq.as<float>(), M, usb, q->mod_index, dy, e.stream);
+        k::delay_hist(dx, q->hbh.in(), q->hbh.out(), n, H, e.stream);
         q->post.mark(e.stream);
-        q->hcur = 1 - q->hcur;
+        q->hbh.flip();
         return;
     }
     const int L = 2 * M + 1;
@@ -2865,11 +2904,11 @@ static void amp_ssb(AmpObj* q, const Exec& e, const void* dx, size_t n, float* d
     void* v1 = q->v1[sl].ensure(n * 8, q->device);
     q->post.wait(e.stream);
     k::ssb_v1(mbuf, dx, dhist, M, q->dtab.as<float>(), n, v1, e.stream);
-    k::ssb_c2r(v1, q->hbh[q->hcur].p, n, q->dhq.as<float>(), M, usb, q->mod_index, mbuf, e.stream);
-    k::delay_hist(v1, q->hbh[q->hcur].p, q->hbh[1 - q->hcur].p, n, H, e.stream);
-    k::fir_exact(false, mbuf, q->dch[q->cur].p, q->dch[1 - q->cur].p, n, q->ddc.as<float>(), L, 1.0f, dy, e.stream);
+    k::ssb_c2r(v1, q->hbh.in(), n, q->dhq.as<float>(), M, usb, q->mod_index, mbuf, e.stream);
+    k::delay_hist(v1, q->hbh.in(), q->hbh.out(), n, H, e.stream);
+    k::fir_exact(false, mbuf, q->dch.in(), q->dch.out(), n, q->ddc.as<float>(), L, 1.0f, dy, e.stream);
     q->post.mark(e.stream);
-    q->hcur = 1 - q->hcur;
+    q->hbh.flip();
     amp_call_end(q, e);
 }
 
@@ -2881,17 +2920,14 @@ int ldsp_ampmodem_demodulate(ldsp_ampmodem_t q, const void* x, size_t n, void* y
         LDSP_REQUIRE(n == 0 || (x && y), "ampmodem_demodulate: NULL buffer");
         if (n > kAmpPieceMax) {              // the walker's 32-bit store offsets: consecutive sub-calls
             for (size_t off = 0; off < n; off += kAmpPieceMax) {
-                const int rc = ldsp_ampmodem_demodulate(q, (const char*)x + off * 8, std::min(kAmpPieceMax, n - off),
-                                                        (char*)y + off * 4, mem, stream);
-                if (rc != LDSP_OK) throw Error(rc, g_last_error);
+                ok(ldsp_ampmodem_demodulate(q, (const char*)x + off * 8, std::min(kAmpPieceMax, n - off),
+                                            (char*)y + off * 4, mem, stream));
             }
             return;
         }
         amp_check_err(q);
-        const BufDevice bd(mem, x);
-        q->ensure_device();
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
+        Call call(*q, mem, x, stream, false);     // the PLL stage orders its parts itself: amp_pll_stage, amp_call_end
+        const Exec& e = call.e;
         const void* dx = q->stg.dev_in(e, x, n * 8);
         float* dy = (float*)q->stg.dev_out(e, y, n * 4);
         if (n > 0 && q->type != 0) {
@@ -2903,24 +2939,30 @@ int ldsp_ampmodem_demodulate(ldsp_ampmodem_t q, const void* x, size_t n, void* y
                 // the DC blocker is off the walker's chain: the next call's walk
                 // waits for this walk only (ord), the next DC blocker for this one
                 q->post.wait(e.stream);
-                k::fir_exact(false, mbuf, q->dch[q->cur].p, q->dch[1 - q->cur].p, n, q->ddc.as<float>(), L, 1.0f,
-                             dy, e.stream);
+                k::fir_exact(false, mbuf, q->dch.in(), q->dch.out(), n, q->ddc.as<float>(), L, 1.0f, dy, e.stream);
                 q->post.mark(e.stream);
             }
             amp_call_end(q, e);
         }
-        q->last = e.stream;
+        call.end();
         q->stg.finish(e, y, n * 4);
         if (e.host) amp_check_err(q);         // synchronised: this call's own walk is done
     });
 }
 
+int ldsp_debug_ampmodem_dispatch(ldsp_ampmodem_t q, size_t n, int* parallel, int* batchable)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (parallel) *parallel = k::pll_parallel(n, q->suppressed ? 1 : 0) ? 1 : 0;
+        if (batchable) *batchable = q->type == 0 ? 1 : 0;
+    });
+}
 int ldsp_debug_ampmodem_handoff(ldsp_ampmodem_t q, uint64_t wait_ticks, int epoch_skew)
 {
     return guard([&] {
         NONNULL(q);
-        q->ensure_device();
-        DeviceGuard g(q->device);
+        DeviceGuard g(DevObj::bind_first(*q, current_device()));
         q->sync_all();
         q->st.wait_ticks = wait_ticks ? (unsigned long long)wait_ticks : kWalkWaitTicks;
         LDSP_HIP(hipMemcpy((char*)q->dst.p + offsetof(k::AmpState, wait_ticks), &q->st.wait_ticks,
@@ -2944,35 +2986,24 @@ int ldsp_bcastam_create(unsigned int m, ldsp_bcastam_t* q)
         o->table = nco_table();
         o->reset_host();
         // cheby2 highpass, SOS, order 3, fc 20/48000, f0 0, Ap 0.5, As 20 (demod.hpp:104)
-        int rc = ldsp_iirfilt_create_prototype(2, 1, 3, 20.0f / 48000.0f, 0.0f, 0.5f, 20.0f, 0, &o->dcb);
-        if (rc != LDSP_OK) throw Error(rc, g_last_error);
+        ok(ldsp_iirfilt_create_prototype(2, 1, 3, 20.0f / 48000.0f, 0.0f, 0.5f, 20.0f, 0, &o->dcb));
         *q = o.release();
     });
 }
-int ldsp_bcastam_destroy(ldsp_bcastam_t q)
-{
-    return guard([&] {
-        if (!q) return;
-        if (q->last) (void)hipStreamSynchronize(q->last);
-        ldsp_iirfilt_destroy(q->dcb);
-        delete q;
-    });
-}
+int ldsp_bcastam_destroy(ldsp_bcastam_t q) { return guard([&] { destroy(q); }); }   // and its DC blocker
 int ldsp_bcastam_reset(ldsp_bcastam_t q)
 {
     return guard([&] {
         NONNULL(q);
         amp_reset(q);
-        const int rc = ldsp_iirfilt_reset(q->dcb);
-        if (rc != LDSP_OK) throw Error(rc, g_last_error);
+        ok(ldsp_iirfilt_reset(q->dcb));
     });
 }
 int ldsp_bcastam_set_mode(ldsp_bcastam_t q, int mode)
 {
     return guard([&] {
         NONNULL(q);
-        const int rc = ldsp_iirfilt_set_mode(q->dcb, mode);
-        if (rc != LDSP_OK) throw Error(rc, g_last_error);
+        ok(ldsp_iirfilt_set_mode(q->dcb, mode));
     });
 }
 int ldsp_bcastam_get_mode(ldsp_bcastam_t q, int* mode)
@@ -2992,30 +3023,26 @@ int ldsp_bcastam_demodulate(ldsp_bcastam_t q, const void* x, size_t n, void* y, 
         if (n > kAmpPieceMax) {              // as ldsp_ampmodem_demodulate
             for (size_t off = 0; off < n; off += kAmpPieceMax) {
                 const size_t m = std::min(kAmpPieceMax, n - off);
-                const int rc = ldsp_bcastam_demodulate(q, (const char*)x + off * 8, m, (char*)y + off * 4,
-                                                       pre ? (char*)pre + off * 4 : nullptr, mem, stream);
-                if (rc != LDSP_OK) throw Error(rc, g_last_error);
+                ok(ldsp_bcastam_demodulate(q, (const char*)x + off * 8, m, (char*)y + off * 4,
+                                           pre ? (char*)pre + off * 4 : nullptr, mem, stream));
             }
             return;
         }
         amp_check_err(q);
-        const BufDevice bd(mem, x);
-        q->ensure_device();
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
+        Call call(*q, mem, x, stream, false);     // as ldsp_ampmodem_demodulate
+        const Exec& e = call.e;
         const void* dx = q->stg.dev_in(e, x, n * 8);
         float* dy = (float*)q->stg.dev_out(e, y, n * 4);
         if (n > 0) {
             float* mbuf = amp_pll_stage(q, e, dx, n, 1.0f, 0, nullptr);
-            const int rc = ldsp_iirfilt_execute(q->dcb, mbuf, n, dy, LDSP_MEM_DEVICE, e.stream);
-            if (rc != LDSP_OK) throw Error(rc, g_last_error);
+            ok(ldsp_iirfilt_execute(q->dcb, mbuf, n, dy, LDSP_MEM_DEVICE, e.stream));
             if (pre) {
                 LDSP_HIP(hipMemcpyAsync(pre, mbuf, n * 4, e.host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                                         e.stream));
             }
             amp_call_end(q, e);
         }
-        q->last = e.stream;
+        call.end();
         q->stg.finish(e, y, n * 4);
         if (e.host) amp_check_err(q);
     });
@@ -3033,21 +3060,12 @@ int ldsp_freqdem_create(float kf, ldsp_freqdem_t* q)
         *q = o.release();
     });
 }
-int ldsp_freqdem_destroy(ldsp_freqdem_t q)
-{
-    return guard([&] {
-        if (q && q->last) (void)hipStreamSynchronize(q->last);
-        delete q;
-    });
-}
+int ldsp_freqdem_destroy(ldsp_freqdem_t q) { return guard([&] { destroy(q); }); }
 int ldsp_freqdem_reset(ldsp_freqdem_t q)
 {
     return guard([&] {
         NONNULL(q);
-        if (q->device < 0) return;
-        DeviceGuard g(q->device);
-        if (q->last) LDSP_HIP(hipStreamSynchronize(q->last));
-        for (int i = 0; i < 2; i++) zero_now(q->prev[i].p, 0, 8);
+        q->at_rest([&] { q->prev.zero(8, q->device); });
     });
 }
 int ldsp_freqdem_get_kf(ldsp_freqdem_t q, float* kf)
@@ -3064,23 +3082,15 @@ int ldsp_freqdem_demodulate(ldsp_freqdem_t q, const void* x, size_t n, void* y, 
     return guard([&] {
         NONNULL(q);
         LDSP_REQUIRE(n == 0 || (x && y), "freqdem_demodulate: NULL buffer");
-        const BufDevice bd(mem, x);
-        if (q->device < 0) {
-            const int dev = current_device();
-            for (int i = 0; i < 2; i++) zero_now(q->prev[i].ensure(8, dev), 0, 8);
-            q->device = dev;
-        }
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
-        q->ord.wait(e.stream);
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
         const void* dx = q->stg.dev_in(e, x, n * 8);
         float* dy = (float*)q->stg.dev_out(e, y, n * 4);
         if (n > 0) {
-            k::freqdem(dx, q->prev[q->cur].p, q->prev[1 - q->cur].p, n, q->ref, dy, e.stream);
-            q->cur = 1 - q->cur;
+            k::freqdem(dx, q->prev.in(), q->prev.out(), n, q->ref, dy, e.stream);
+            q->prev.flip();
         }
-        q->ord.mark(e.stream);
-        q->last = e.stream;
+        call.end();
         q->stg.finish(e, y, n * 4);
     });
 }
@@ -3096,23 +3106,14 @@ int ldsp_delay_create(unsigned int nd, ldsp_delay_t* q)
         *q = o.release();
     });
 }
-int ldsp_delay_destroy(ldsp_delay_t q)
-{
-    return guard([&] {
-        if (q && q->last) (void)hipStreamSynchronize(q->last);
-        delete q;
-    });
-}
+int ldsp_delay_destroy(ldsp_delay_t q) { return guard([&] { destroy(q); }); }
 int ldsp_delay_set_delay(ldsp_delay_t q, unsigned int nd)
 {
     return guard([&] {
         NONNULL(q);
         LDSP_REQUIRE(nd <= (1u << 26), "delay: nd too large");
         q->nd = nd;
-        if (q->device < 0) return;
-        DeviceGuard g(q->device);
-        if (q->last) LDSP_HIP(hipStreamSynchronize(q->last));
-        q->zero();
+        q->at_rest([&] { q->zero(q->device); });
     });
 }
 int ldsp_delay_get_delay(ldsp_delay_t q, unsigned int* nd)
@@ -3129,27 +3130,18 @@ int ldsp_delay_execute(ldsp_delay_t q, const void* x, size_t n, int cplx, void* 
     return guard([&] {
         NONNULL(q);
         LDSP_REQUIRE(n == 0 || (x && y), "delay_execute: NULL buffer");
-        const BufDevice bd(mem, x);
-        if (q->device < 0) {
-            q->device = current_device();
-            DeviceGuard g(q->device);
-            q->zero();
-        }
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
-        q->ord.wait(e.stream);
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
         const size_t es = cplx ? 8 : 4;
         const void* dx = q->stg.dev_in(e, x, n * es);
         void* dy = q->stg.dev_out(e, y, n * es);
         if (n > 0) {
             const int D = (int)q->nd + 1;
-            int& c = cplx ? q->cc : q->cr;
-            ldsp::DevBuf* h = cplx ? q->hc : q->hr;
-            k::delay(cplx != 0, dx, h[c].p, h[1 - c].p, n, D, dy, e.stream);
-            c = 1 - c;
+            PingPong& h = cplx ? q->hc : q->hr;
+            k::delay(cplx != 0, dx, h.in(), h.out(), n, D, dy, e.stream);
+            h.flip();
         }
-        q->ord.mark(e.stream);
-        q->last = e.stream;
+        call.end();
         q->stg.finish(e, y, n * es);
     });
 }
@@ -3174,22 +3166,12 @@ int ldsp_firhilb_create(unsigned int m, float as, int op, ldsp_firhilb_t* q)
         *q = o.release();
     });
 }
-int ldsp_firhilb_destroy(ldsp_firhilb_t q)
-{
-    return guard([&] {
-        if (q && q->last) (void)hipStreamSynchronize(q->last);
-        delete q;
-    });
-}
+int ldsp_firhilb_destroy(ldsp_firhilb_t q) { return guard([&] { destroy(q); }); }
 int ldsp_firhilb_reset(ldsp_firhilb_t q)
 {
     return guard([&] {
         NONNULL(q);
-        if (q->device < 0) return;
-        DeviceGuard g(q->device);
-        if (q->last) LDSP_HIP(hipStreamSynchronize(q->last));
-        q->ord.sync();
-        q->zero();
+        q->at_rest([&] { q->hist.zero(q->hist_bytes(), q->device); });
     });
 }
 int ldsp_firhilb_get_taps(ldsp_firhilb_t q, float* hq)
@@ -3210,19 +3192,8 @@ int ldsp_firhilb_execute(ldsp_firhilb_t q, const void* x, size_t n, void* y0, vo
         else LDSP_REQUIRE(!y1, "firhilb_execute: y1 must be NULL unless the object is c2r");
         LDSP_REQUIRE(op != LDSP_HILB_DECIM || n % 2 == 0, "firhilb_execute: decim takes an even number of samples");
         LDSP_REQUIRE(n == 0 || (x && (y0 || op == LDSP_HILB_C2R)), "firhilb_execute: NULL buffer");
-        const BufDevice bd(mem, x);
-        if (q->device < 0) {
-            const int dev = current_device();
-            DeviceGuard g(dev);
-            std::vector<float> pad(q->hq);
-            pad.resize(pad.size() + k::kHilbTapPad, 0.0f);
-            upload(q->dhq, pad, dev);
-            q->device = dev;
-            q->zero();
-        }
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
-        q->ord.wait(e.stream);
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
         // output samples and their size
         const size_t no = op == LDSP_HILB_DECIM ? n / 2 : (op == LDSP_HILB_INTERP ? 2 * n : n);
         const size_t os = op == LDSP_HILB_R2C || op == LDSP_HILB_DECIM ? 8 : 4;
@@ -3230,12 +3201,10 @@ int ldsp_firhilb_execute(ldsp_firhilb_t q, const void* x, size_t n, void* y0, vo
         void* d0 = y0 ? q->stg.dev_out(e, y0, no * os) : nullptr;
         void* d1 = y1 ? q->stg1.dev_out(e, y1, no * os) : nullptr;
         if (n > 0) {
-            k::hilbert(op, dx, q->hist[q->cur].p, q->hist[1 - q->cur].p, n, q->dhq.as<float>(), (int)q->m, d0, d1,
-                       e.stream);
-            q->cur = 1 - q->cur;
+            k::hilbert(op, dx, q->hist.in(), q->hist.out(), n, q->dhq.as<float>(), (int)q->m, d0, d1, e.stream);
+            q->hist.flip();
         }
-        q->ord.mark(e.stream);
-        q->last = e.stream;
+        call.end();
         if (y0) q->stg.finish(e, y0, no * os);
         if (y1) q->stg1.finish(e, y1, no * os);
     });
@@ -3249,86 +3218,109 @@ int ldsp_debug_firhilb_tile(int op, size_t* samples)
     });
 }
 
-// ---------------------------------------------------------------- Channelizer
-// exp(2 pi i j / M), j < M, as (re, im) pairs: double, rounded once (k_chan, k_synth)
-static std::vector<float> bank_twiddles(unsigned int M)
+// ---------------------------------------------------------------- Channelizer, Synthesizer
+// What the two banks' entry points do alike takes the words that differ from here.
+struct BankKind {
+    const char* pre;                  // the messages' prefix
+    const char* rate;                 // what D is
+    const char* taps;                 // the taps argument's name
+    bool synth;
+};
+static const BankKind kChan{"chan", "decimation", "h", false}, kSynth{"synth", "interpolation", "g", true};
+
+static void bank_check_channels(const BankKind& kind, unsigned int M)
 {
-    std::vector<float> tw(2 * (size_t)M);
-    for (unsigned j = 0; j < M; j++) {
-        const double a = 2.0 * M_PI * (double)j / (double)M;
-        tw[2 * j] = (float)cos(a);
-        tw[2 * j + 1] = (float)sin(a);
-    }
-    return tw;
+    if (M > 256) throw Error(LDSP_EUNSUP, std::string(kind.pre) + ": more than 256 channels is not implemented");
 }
-static void chan_check_shape(unsigned int M, unsigned int D)
+static void bank_check_shape(const BankKind& kind, unsigned int M, unsigned int D)
 {
-    LDSP_REQUIRE(M >= 4 && (M & (M - 1)) == 0, "chan: the channel count must be a power of two, at least 4");
-    LDSP_REQUIRE(D == M || 2 * D == M, "chan: the decimation must be M (critically sampled) or M / 2 (2x oversampled)");
+    LDSP_REQUIRE(M >= 4 && (M & (M - 1)) == 0,
+                 std::string(kind.pre) + ": the channel count must be a power of two, at least 4");
+    LDSP_REQUIRE(D == M || 2 * D == M, std::string(kind.pre) + ": the " + kind.rate +
+                                           " must be M (critically sampled) or M / 2 (2x oversampled)");
 }
-static ldsp_chan_s* chan_make(unsigned int M, unsigned int D, std::vector<float> h, float scale)
+extern "C++" {
+template <class T>
+static T* bank_make(const BankKind& kind, unsigned int M, unsigned int D, std::vector<float> h, float scale)
 {
-    if (M > 256) throw Error(LDSP_EUNSUP, "chan: more than 256 channels is not implemented");
-    const size_t P = (h.size() + M - 1) / M;
-    if (P > (size_t)k::kChanMaxP)
-        throw Error(LDSP_EUNSUP, "chan: more than " + std::to_string(k::kChanMaxP) + " taps per branch (L > " +
-                                     std::to_string(k::kChanMaxP) + " M) is not implemented");
-    std::unique_ptr<ldsp_chan_s> o(new ldsp_chan_s());
+    bank_check_channels(kind, M);
+    if (h.size() > (size_t)k::kChanMaxP * M)
+        throw Error(LDSP_EUNSUP, std::string(kind.pre) + ": more than " + std::to_string(k::kChanMaxP) +
+                                     " taps per branch (L > " + std::to_string(k::kChanMaxP) + " M) is not implemented");
+    std::unique_ptr<T> o(new T());
     o->M = M;
     o->D = D;
-    o->P = (unsigned)P;
+    o->R = (unsigned)((h.size() + (kind.synth ? D : M) - 1) / (kind.synth ? D : M));
+    o->hist_bytes = (kind.synth ? std::max<size_t>((size_t)M * (o->R - 1), 1) : (size_t)o->R * M - 1) * 8;
     o->h = std::move(h);
     o->scale = scale;
     return o.release();
 }
-int ldsp_chan_create(unsigned int M, unsigned int D, unsigned int m, float fc, float as, ldsp_chan_t* q)
+template <class T>
+static int bank_create_taps(const BankKind& kind, unsigned int M, unsigned int D, const float* h, unsigned int L, T** q)
 {
     return guard([&] {
         NONNULL(q);
-        chan_check_shape(M, D);
-        LDSP_REQUIRE(m >= 1, "chan: filter semi-length must be at least 1");
-        LDSP_REQUIRE(as > 0.0f, "chan: stop-band attenuation must be > 0");
-        LDSP_REQUIRE(fc < 0.5f, "chan: cutoff must be below 0.5");
-        if (M > 256) throw Error(LDSP_EUNSUP, "chan: more than 256 channels is not implemented");
-        if (2 * (size_t)m + 1 > (size_t)k::kChanMaxP)
-            throw Error(LDSP_EUNSUP, "chan: semi-length above " + std::to_string((k::kChanMaxP - 1) / 2) +
-                                         " is not implemented");
-        if (!(fc > 0.0f)) fc = 0.5f / (float)M;
-        std::vector<float> h = design::firdes_kaiser(2 * M * m + 1, fc, as, 0.0f);
-        double sum = 0.0;
-        for (float v : h) sum += (double)v;
-        *q = chan_make(M, D, std::move(h), (float)(1.0 / sum));
+        bank_check_shape(kind, M, D);
+        LDSP_REQUIRE(L >= 1, std::string(kind.pre) + ": at least one tap");
+        LDSP_REQUIRE(h != nullptr, std::string(kind.taps) + " must not be NULL");
+        *q = bank_make<T>(kind, M, D, std::vector<float>(h, h + L), 1.0f);
     });
 }
-int ldsp_chan_create_taps(unsigned int M, unsigned int D, const float* h, unsigned int L, ldsp_chan_t* q)
+} // extern "C++"
+// The Kaiser prototype of 2 M m + 1 taps and their sum in double; a cutoff that
+// is not positive stands for the bank's default `fc0`.
+static std::vector<float> bank_prototype(const BankKind& kind, unsigned int M, unsigned int m, float fc, float fc0,
+                                         float as, double* sum)
 {
-    return guard([&] {
-        NONNULL(q);
-        chan_check_shape(M, D);
-        LDSP_REQUIRE(L >= 1, "chan: at least one tap");
-        NONNULL(h);
-        *q = chan_make(M, D, std::vector<float>(h, h + L), 1.0f);
-    });
+    const std::string pre(kind.pre);
+    LDSP_REQUIRE(m >= 1, pre + ": filter semi-length must be at least 1");
+    LDSP_REQUIRE(as > 0.0f, pre + ": stop-band attenuation must be > 0");
+    LDSP_REQUIRE(fc < 0.5f, pre + ": cutoff must be below 0.5");
+    bank_check_channels(kind, M);
+    if (2 * (size_t)m + 1 > (size_t)k::kChanMaxP)
+        throw Error(LDSP_EUNSUP, pre + ": semi-length above " + std::to_string((k::kChanMaxP - 1) / 2) +
+                                     " is not implemented");
+    std::vector<float> h = design::firdes_kaiser(2 * M * m + 1, fc > 0.0f ? fc : fc0, as, 0.0f);
+    *sum = 0.0;
+    for (float v : h) *sum += (double)v;
+    return h;
 }
-int ldsp_chan_destroy(ldsp_chan_t q)
-{
-    return guard([&] {
-        if (q && q->last) (void)hipStreamSynchronize(q->last);
-        delete q;
-    });
-}
-int ldsp_chan_reset(ldsp_chan_t q)
+static int bank_reset(BankObj* q)
 {
     return guard([&] {
         NONNULL(q);
         q->seen = 0;
-        if (q->device < 0) return;
-        DeviceGuard g(q->device);
-        if (q->last) LDSP_HIP(hipStreamSynchronize(q->last));
-        q->ord.sync();
-        q->zero();
+        q->at_rest([&] { q->hist.zero(q->hist_bytes, q->device); });
     });
 }
+static int bank_get_taps(const BankKind& kind, const BankObj* q, float* h)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(h != nullptr, std::string(kind.taps) + " must not be NULL");
+        std::copy(q->h.begin(), q->h.end(), h);
+    });
+}
+static int bank_get_scale(const BankObj* q, float* s) { return guard([&] { NONNULL(q); NONNULL(s); *s = q->scale; }); }
+static int bank_set_scale(BankObj* q, float s) { return guard([&] { NONNULL(q); q->scale = s; }); }
+
+int ldsp_chan_create(unsigned int M, unsigned int D, unsigned int m, float fc, float as, ldsp_chan_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        bank_check_shape(kChan, M, D);
+        double sum = 0.0;
+        std::vector<float> h = bank_prototype(kChan, M, m, fc, 0.5f / (float)M, as, &sum);
+        *q = bank_make<ldsp_chan_s>(kChan, M, D, std::move(h), (float)(1.0 / sum));
+    });
+}
+int ldsp_chan_create_taps(unsigned int M, unsigned int D, const float* h, unsigned int L, ldsp_chan_t* q)
+{
+    return bank_create_taps(kChan, M, D, h, L, q);
+}
+int ldsp_chan_destroy(ldsp_chan_t q) { return guard([&] { destroy(q); }); }
+int ldsp_chan_reset(ldsp_chan_t q) { return bank_reset(q); }
 int ldsp_chan_get_info(ldsp_chan_t q, unsigned int* M, unsigned int* D, unsigned int* L, unsigned int* skip)
 {
     return guard([&] {
@@ -3339,16 +3331,9 @@ int ldsp_chan_get_info(ldsp_chan_t q, unsigned int* M, unsigned int* D, unsigned
         if (skip) *skip = (unsigned)q->skip();
     });
 }
-int ldsp_chan_get_taps(ldsp_chan_t q, float* h)
-{
-    return guard([&] {
-        NONNULL(q);
-        NONNULL(h);
-        std::copy(q->h.begin(), q->h.end(), h);
-    });
-}
-int ldsp_chan_get_scale(ldsp_chan_t q, float* s) { return guard([&] { NONNULL(q); NONNULL(s); *s = q->scale; }); }
-int ldsp_chan_set_scale(ldsp_chan_t q, float s) { return guard([&] { NONNULL(q); q->scale = s; }); }
+int ldsp_chan_get_taps(ldsp_chan_t q, float* h) { return bank_get_taps(kChan, q, h); }
+int ldsp_chan_get_scale(ldsp_chan_t q, float* s) { return bank_get_scale(q, s); }
+int ldsp_chan_set_scale(ldsp_chan_t q, float s) { return bank_set_scale(q, s); }
 int ldsp_chan_num_outputs(ldsp_chan_t q, size_t n, size_t* ncols)
 {
     return guard([&] {
@@ -3367,154 +3352,76 @@ int ldsp_chan_execute(ldsp_chan_t q, const void* x, size_t n, void* y, size_t ld
         if (K > ld) throw Error(LDSP_ERANGE, "chan_execute: row stride below the number of output columns");
         LDSP_REQUIRE(n == 0 || x, "chan_execute: NULL input");
         LDSP_REQUIRE(K == 0 || y, "chan_execute: NULL output");
-        LDSP_REQUIRE(mem == LDSP_MEM_HOST || mem == LDSP_MEM_DEVICE, "mem must be LDSP_MEM_HOST or LDSP_MEM_DEVICE");
-        const BufDevice bd(mem, x);
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
         const unsigned M = q->M, D = q->D;
-        if (q->device < 0) {
-            const int dev = current_device();
-            DeviceGuard g(dev);
-            std::vector<float> pad(q->h);
-            pad.resize((size_t)k::kChanMaxP * M, 0.0f);
-            upload(q->dtaps, pad, dev);
-            upload(q->dtw, bank_twiddles(M), dev);
-            q->device = dev;
-            q->zero();
-        }
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
-        q->ord.wait(e.stream);
         // a host-memory call computes into a dense [M][K] device image
+        // (rows of the caller's image are ld samples apart)
         const size_t dld = e.host ? K : ld;
         const void* dx = q->stg.dev_in(e, x, n * 8);
         void* dy = q->stg.dev_out(e, y, (size_t)M * K * 8);
         if (n > 0) {
             k::ChanCall c;
             c.x = dx;
-            c.hist = q->hist[q->cur].p;
-            c.hist_out = q->hist[1 - q->cur].p;
+            c.hist = q->hist.in();
+            c.hist_out = q->hist.out();
             c.n = n;
             c.skip = q->skip();
             c.ncols = K;
             c.ld = dld;
             c.parity = q->parity();
-            c.P = (int)q->P;
+            c.P = (int)q->R;
             c.taps = q->dtaps.as<float>();
             c.tw = q->dtw.p;
             c.scale = q->scale;
             c.y = dy;
             k::chan((int)M, (int)D, c, e.stream);
-            q->cur = 1 - q->cur;
+            q->hist.flip();
             q->seen += n;
         }
-        q->ord.mark(e.stream);
-        q->last = e.stream;
-        if (e.host && ld != K && K > 0) {
-            // rows of the caller's image are ld samples apart
-            LDSP_HIP(hipMemcpy2DAsync(y, ld * 8, dy, K * 8, K * 8, M, hipMemcpyDeviceToHost, e.stream));
-            LDSP_HIP(hipStreamSynchronize(e.stream));
-        } else {
-            q->stg.finish(e, y, (size_t)M * K * 8);
-        }
+        call.end();
+        q->stg.finish(e, y, K * 8, M, ld * 8);
     });
 }
 int ldsp_debug_chan_tile(unsigned int M, unsigned int D, size_t* frames)
 {
     return guard([&] {
         NONNULL(frames);
-        chan_check_shape(M, D);
-        if (M > 256) throw Error(LDSP_EUNSUP, "chan: more than 256 channels is not implemented");
+        bank_check_shape(kChan, M, D);
+        bank_check_channels(kChan, M);
         *frames = (size_t)k::chan_frames((int)M);
     });
 }
 
-// ---------------------------------------------------------------- Synthesizer
-static void synth_check_shape(unsigned int M, unsigned int D)
-{
-    LDSP_REQUIRE(M >= 4 && (M & (M - 1)) == 0, "synth: the channel count must be a power of two, at least 4");
-    LDSP_REQUIRE(D == M || 2 * D == M, "synth: the interpolation must be M (critically sampled) or M / 2 (2x oversampled)");
-}
-static ldsp_synth_s* synth_make(unsigned int M, unsigned int D, std::vector<float> g, float scale)
-{
-    if (M > 256) throw Error(LDSP_EUNSUP, "synth: more than 256 channels is not implemented");
-    if (g.size() > (size_t)k::kChanMaxP * M)
-        throw Error(LDSP_EUNSUP, "synth: more than " + std::to_string(k::kChanMaxP) + " taps per branch (L > " +
-                                     std::to_string(k::kChanMaxP) + " M) is not implemented");
-    std::unique_ptr<ldsp_synth_s> o(new ldsp_synth_s());
-    o->M = M;
-    o->D = D;
-    o->Q = (unsigned)((g.size() + D - 1) / D);
-    o->g = std::move(g);
-    o->scale = scale;
-    return o.release();
-}
 int ldsp_synth_create(unsigned int M, unsigned int D, unsigned int m, float fc, float as, ldsp_synth_t* q)
 {
     return guard([&] {
         NONNULL(q);
-        synth_check_shape(M, D);
-        LDSP_REQUIRE(m >= 1, "synth: filter semi-length must be at least 1");
-        LDSP_REQUIRE(as > 0.0f, "synth: stop-band attenuation must be > 0");
-        LDSP_REQUIRE(fc < 0.5f, "synth: cutoff must be below 0.5");
-        if (M > 256) throw Error(LDSP_EUNSUP, "synth: more than 256 channels is not implemented");
-        if (2 * (size_t)m + 1 > (size_t)k::kChanMaxP)
-            throw Error(LDSP_EUNSUP, "synth: semi-length above " + std::to_string((k::kChanMaxP - 1) / 2) +
-                                         " is not implemented");
+        bank_check_shape(kSynth, M, D);
         // D = M / 2: flat across the analysis prototype's transition band, stopped before the image at 2 / M
-        if (!(fc > 0.0f)) fc = (D == M ? 0.5f : 1.0f) / (float)M;
-        std::vector<float> g = design::firdes_kaiser(2 * M * m + 1, fc, as, 0.0f);
         double sum = 0.0;
-        for (float v : g) sum += (double)v;
-        *q = synth_make(M, D, std::move(g), (float)((double)D / sum));
+        std::vector<float> g = bank_prototype(kSynth, M, m, fc, (D == M ? 0.5f : 1.0f) / (float)M, as, &sum);
+        *q = bank_make<ldsp_synth_s>(kSynth, M, D, std::move(g), (float)((double)D / sum));
     });
 }
 int ldsp_synth_create_taps(unsigned int M, unsigned int D, const float* g, unsigned int L, ldsp_synth_t* q)
 {
-    return guard([&] {
-        NONNULL(q);
-        synth_check_shape(M, D);
-        LDSP_REQUIRE(L >= 1, "synth: at least one tap");
-        NONNULL(g);
-        *q = synth_make(M, D, std::vector<float>(g, g + L), 1.0f);
-    });
+    return bank_create_taps(kSynth, M, D, g, L, q);
 }
-int ldsp_synth_destroy(ldsp_synth_t q)
-{
-    return guard([&] {
-        if (q && q->last) (void)hipStreamSynchronize(q->last);
-        delete q;
-    });
-}
-int ldsp_synth_reset(ldsp_synth_t q)
-{
-    return guard([&] {
-        NONNULL(q);
-        q->seen = 0;
-        if (q->device < 0) return;
-        DeviceGuard g(q->device);
-        if (q->last) LDSP_HIP(hipStreamSynchronize(q->last));
-        q->ord.sync();
-        q->zero();
-    });
-}
+int ldsp_synth_destroy(ldsp_synth_t q) { return guard([&] { destroy(q); }); }
+int ldsp_synth_reset(ldsp_synth_t q) { return bank_reset(q); }
 int ldsp_synth_get_info(ldsp_synth_t q, unsigned int* M, unsigned int* D, unsigned int* L)
 {
     return guard([&] {
         NONNULL(q);
         if (M) *M = q->M;
         if (D) *D = q->D;
-        if (L) *L = (unsigned)q->g.size();
+        if (L) *L = (unsigned)q->h.size();
     });
 }
-int ldsp_synth_get_taps(ldsp_synth_t q, float* g)
-{
-    return guard([&] {
-        NONNULL(q);
-        NONNULL(g);
-        std::copy(q->g.begin(), q->g.end(), g);
-    });
-}
-int ldsp_synth_get_scale(ldsp_synth_t q, float* s) { return guard([&] { NONNULL(q); NONNULL(s); *s = q->scale; }); }
-int ldsp_synth_set_scale(ldsp_synth_t q, float s) { return guard([&] { NONNULL(q); q->scale = s; }); }
+int ldsp_synth_get_taps(ldsp_synth_t q, float* g) { return bank_get_taps(kSynth, q, g); }
+int ldsp_synth_get_scale(ldsp_synth_t q, float* s) { return bank_get_scale(q, s); }
+int ldsp_synth_set_scale(ldsp_synth_t q, float s) { return bank_set_scale(q, s); }
 int ldsp_synth_num_outputs(ldsp_synth_t q, size_t ncols, size_t* n)
 {
     return guard([&] {
@@ -3536,52 +3443,31 @@ int ldsp_synth_execute(ldsp_synth_t q, const void* y, size_t ld, size_t ncols, v
         if (cap < N) throw Error(LDSP_ERANGE, "synth_execute: output capacity below ncols * D");
         LDSP_REQUIRE(K == 0 || y, "synth_execute: NULL input");
         LDSP_REQUIRE(K == 0 || z, "synth_execute: NULL output");
-        LDSP_REQUIRE(mem == LDSP_MEM_HOST || mem == LDSP_MEM_DEVICE, "mem must be LDSP_MEM_HOST or LDSP_MEM_DEVICE");
-        const BufDevice bd(mem, y);
-        if (q->device < 0) {
-            const int dev = current_device();
-            DeviceGuard g(dev);
-            std::vector<float> pad(q->g);
-            pad.resize((size_t)k::kChanMaxP * M, 0.0f);
-            upload(q->dtaps, pad, dev);
-            upload(q->dtw, bank_twiddles(M), dev);
-            q->device = dev;
-            q->zero();
-        }
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
-        q->ord.wait(e.stream);
+        Call call(*q, mem, y, stream);
+        const Exec& e = call.e;
         // a host-memory call reads a dense [M][K] device image
+        // (rows of the caller's image are ld samples apart)
         const size_t dld = e.host ? K : ld;
-        const void* dy;
-        if (e.host && ld != K && K > 0) {
-            // rows of the caller's image are ld samples apart
-            void* in = q->stg.in.ensure((size_t)M * K * 8, e.device);
-            LDSP_HIP(hipMemcpy2DAsync(in, K * 8, y, ld * 8, K * 8, M, hipMemcpyHostToDevice, e.stream));
-            dy = in;
-        } else {
-            dy = q->stg.dev_in(e, y, (size_t)M * K * 8);
-        }
+        const void* dy = q->stg.dev_in(e, y, K * 8, M, ld * 8);
         void* dz = q->stg.dev_out(e, z, N * 8);
         if (K > 0) {
             k::SynthCall c;
             c.y = dy;
-            c.hist = q->hist[q->cur].p;
-            c.hist_out = q->hist[1 - q->cur].p;
+            c.hist = q->hist.in();
+            c.hist_out = q->hist.out();
             c.ncols = K;
             c.ld = dld;
             c.parity = (int)(q->seen & 1);
-            c.Q = (int)q->Q;
+            c.Q = (int)q->R;
             c.taps = q->dtaps.as<float>();
             c.tw = q->dtw.p;
             c.scale = q->scale;
             c.z = dz;
             k::synth((int)M, (int)D, c, e.stream);
-            q->cur = 1 - q->cur;
+            q->hist.flip();
             q->seen += K;
         }
-        q->ord.mark(e.stream);
-        q->last = e.stream;
+        call.end();
         q->stg.finish(e, z, N * 8);
     });
 }
@@ -3589,8 +3475,8 @@ int ldsp_debug_synth_tile(unsigned int M, unsigned int D, size_t* cols)
 {
     return guard([&] {
         NONNULL(cols);
-        synth_check_shape(M, D);
-        if (M > 256) throw Error(LDSP_EUNSUP, "synth: more than 256 channels is not implemented");
+        bank_check_shape(kSynth, M, D);
+        bank_check_channels(kSynth, M);
         *cols = (size_t)k::synth_cols((int)M);
     });
 }
@@ -3656,29 +3542,17 @@ int ldsp_spgram_create_window(unsigned int nfft, const float* w, unsigned int W,
         *q = spgram_make(nfft, W, d, A, std::vector<float>(w, w + W));
     });
 }
-int ldsp_spgram_destroy(ldsp_spgram_t q)
-{
-    return guard([&] {
-        if (q && q->last) (void)hipStreamSynchronize(q->last);
-        delete q;
-    });
-}
-static void spgram_quiesce(ldsp_spgram_s* q)
-{
-    if (q->last) LDSP_HIP(hipStreamSynchronize(q->last));
-    q->ord.sync();
-}
+int ldsp_spgram_destroy(ldsp_spgram_t q) { return guard([&] { destroy(q); }); }
 int ldsp_spgram_reset(ldsp_spgram_t q)
 {
     return guard([&] {
         NONNULL(q);
         q->seen = 0;
         q->nacc = 0;
-        if (q->device < 0) return;
-        DeviceGuard g(q->device);
-        spgram_quiesce(q);
-        q->zero_stream();
-        q->zero_psd();
+        q->at_rest([&] {
+            q->zero_stream(q->device);
+            q->zero_psd(q->device);
+        });
     });
 }
 int ldsp_spgram_clear(ldsp_spgram_t q)
@@ -3686,10 +3560,7 @@ int ldsp_spgram_clear(ldsp_spgram_t q)
     return guard([&] {
         NONNULL(q);
         q->nacc = 0;
-        if (q->device < 0) return;
-        DeviceGuard g(q->device);
-        spgram_quiesce(q);
-        q->zero_psd();
+        q->at_rest([&] { q->zero_psd(q->device); });
     });
 }
 int ldsp_spgram_get_info(ldsp_spgram_t q, unsigned int* nfft, unsigned int* W, unsigned int* d, unsigned int* A,
@@ -3732,8 +3603,8 @@ static void spgram_piece(ldsp_spgram_s* q, const void* dx, size_t n, float* dy, 
     const size_t nb = (size_t)(s1 / A - s0 / A);                         // its finished rows: blocks when blocked
     k::SpgramCall c;
     c.x = dx;
-    c.hist = q->hist[q->cur].p;
-    c.hist_out = q->hist[1 - q->cur].p;
+    c.hist = q->hist.in();
+    c.hist_out = q->hist.out();
     c.n = n;
     c.A = A;
     c.a0 = (size_t)(s0 % A);
@@ -3744,22 +3615,21 @@ static void spgram_piece(ldsp_spgram_s* q, const void* dx, size_t n, float* dy, 
     c.d = (int)q->d;
     c.win = q->dwin.as<float>();
     c.tw = q->dtw.p;
-    c.carry_in = q->carry[q->ccur].as<float>();
-    c.carry_out = q->carry[1 - q->ccur].as<float>();
+    c.carry_in = (float*)q->carry.in();
+    c.carry_out = (float*)q->carry.out();
     c.scale = blocked ? 1.0f : 1.0f / (float)q->A;
     c.y = blocked ? (float*)q->blk.ensure(std::max<size_t>(nb, 1) * N * 4, q->device) : dy;
     const size_t runs = k::spgram_runs((int)N, c.A, c.a0, nt, nullptr);
     c.part = (float*)q->part.ensure(std::max<size_t>(runs, 1) * N * 4, q->device);
     c.psd = q->dpsd.as<double>();
     k::spgram((int)N, c, stream);
-    q->cur = 1 - q->cur;
+    q->hist.flip();
     // the unfinished row (block) moved to the other buffer if the piece left one behind
-    if (nt > 0 && s1 % A != 0) q->ccur = 1 - q->ccur;
+    if (nt > 0 && s1 % A != 0) q->carry.flip();
     if (blocked && nb > 0) {
         const size_t M = q->A / A, c0 = (size_t)((s0 / A) % M);
-        k::spgram_rows((int)N, c.y, nb, M, c0, q->rcarry[q->rcur].as<float>(), q->rcarry[1 - q->rcur].as<float>(),
-                       q->A, dy, dld, stream);
-        if ((c0 + nb) % M != 0) q->rcur = 1 - q->rcur;
+        k::spgram_rows((int)N, c.y, nb, M, c0, (float*)q->rcarry.in(), (float*)q->rcarry.out(), q->A, dy, dld, stream);
+        if ((c0 + nb) % M != 0) q->rcarry.flip();
     }
     q->seen += n;
     q->nacc += nt;
@@ -3773,31 +3643,13 @@ int ldsp_spgram_execute(ldsp_spgram_t q, const void* x, size_t n, float* y, size
         const size_t K = q->rows(n);
         if (nrows) *nrows = K;
         LDSP_REQUIRE(n == 0 || x, "spgram_execute: NULL input");
-        LDSP_REQUIRE(mem == LDSP_MEM_HOST || mem == LDSP_MEM_DEVICE, "mem must be LDSP_MEM_HOST or LDSP_MEM_DEVICE");
+        checked_mem(mem);                      // (reported before the stride)
         LDSP_REQUIRE(!y || ld >= q->N, "spgram_execute: row stride below nfft");
-        const BufDevice bd(mem, x);
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
         const unsigned N = q->N;
-        if (q->device < 0) {
-            const int dev = current_device();
-            DeviceGuard g(dev);
-            std::vector<float> pad(q->w);
-            pad.resize(N, 0.0f);
-            upload(q->dwin, pad, dev);
-            std::vector<float> tw(2 * (size_t)N);             // exp(-2 pi i j / N): double, rounded once
-            for (unsigned j = 0; j < N; j++) {
-                const double a = -2.0 * M_PI * (double)j / (double)N;
-                tw[2 * j] = (float)cos(a);
-                tw[2 * j + 1] = (float)sin(a);
-            }
-            upload(q->dtw, tw, dev);
-            q->device = dev;
-            q->zero_stream();
-            q->zero_psd();
-        }
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
-        q->ord.wait(e.stream);
         // a host-memory call computes into a dense [K][N] device image
+        // (rows of the caller's image are ld floats apart)
         const bool rows_out = y != nullptr && K > 0;
         const size_t dld = e.host ? N : ld;
         const void* dx = q->stg.dev_in(e, x, n * 8);
@@ -3815,15 +3667,8 @@ int ldsp_spgram_execute(ldsp_spgram_t q, const void* x, size_t n, float* y, size
             if (dy) dy += done * dld;
             off += m;
         }
-        q->ord.mark(e.stream);
-        q->last = e.stream;
-        if (e.host && rows_out && ld != N) {
-            // rows of the caller's image are ld floats apart
-            LDSP_HIP(hipMemcpy2DAsync(y, ld * 4, dy0, (size_t)N * 4, (size_t)N * 4, K, hipMemcpyDeviceToHost, e.stream));
-            LDSP_HIP(hipStreamSynchronize(e.stream));
-        } else {
-            q->stg.finish(e, y, rows_out ? K * (size_t)N * 4 : 0);
-        }
+        call.end();
+        q->stg.finish(e, y, (size_t)N * 4, rows_out ? K : 0, ld * 4);
     });
 }
 int ldsp_spgram_get_psd(ldsp_spgram_t q, double* psd, uint64_t* transforms)
@@ -3833,12 +3678,12 @@ int ldsp_spgram_get_psd(ldsp_spgram_t q, double* psd, uint64_t* transforms)
         NONNULL(psd);
         if (transforms) *transforms = q->nacc;
         std::fill(psd, psd + q->N, 0.0);
-        if (q->nacc == 0 || q->device < 0) return;
-        DeviceGuard g(q->device);
-        spgram_quiesce(q);
-        LDSP_HIP(hipMemcpy(psd, q->dpsd.p, (size_t)q->N * 8, hipMemcpyDeviceToHost));
-        const double s = (double)q->nacc;
-        for (unsigned k = 0; k < q->N; k++) psd[k] /= s;
+        if (q->nacc == 0) return;
+        q->at_rest([&] {
+            LDSP_HIP(hipMemcpy(psd, q->dpsd.p, (size_t)q->N * 8, hipMemcpyDeviceToHost));
+            const double s = (double)q->nacc;
+            for (unsigned k = 0; k < q->N; k++) psd[k] /= s;
+        });
     });
 }
 int ldsp_debug_spgram_tile(unsigned int nfft, size_t* transforms)
@@ -3868,9 +3713,6 @@ int ldsp_fmstereo_create(float iq_rate, float pcm_rate, ldsp_fmstereo_t* q)
         a[0] = 1.0;
         a[1] = -exp(-1.0 / (75.0E-6 * iq_rate));
         b[0] = 1.0 + a[1];
-        auto ok = [](int rc) {
-            if (rc != LDSP_OK) throw Error(rc, g_last_error);
-        };
         ok(ldsp_freqdem_create(4.0f, &o->dem));
         for (int c = 0; c < 2; c++) {
             ok(ldsp_iirfilt_create_tf(b, 1, a, 2, 0, &o->emph[c]));
@@ -3886,27 +3728,12 @@ int ldsp_fmstereo_create(float iq_rate, float pcm_rate, ldsp_fmstereo_t* q)
         *q = o.release();
     });
 }
-int ldsp_fmstereo_destroy(ldsp_fmstereo_t q)
-{
-    return guard([&] {
-        if (!q) return;
-        if (q->last) (void)hipStreamSynchronize(q->last);
-        ldsp_freqdem_destroy(q->dem);
-        for (int c = 0; c < 2; c++) {
-            ldsp_iirfilt_destroy(q->emph[c]);
-            ldsp_resamp_destroy(q->aud[c]);
-        }
-        delete q;
-    });
-}
+int ldsp_fmstereo_destroy(ldsp_fmstereo_t q) { return guard([&] { destroy(q); }); }   // and its stages
 int ldsp_fmstereo_reset(ldsp_fmstereo_t q)
 {
     return guard([&] {
         NONNULL(q);
-        for (int c = 0; c < 2; c++) {   // demod.hpp:34-37: only the resamplers
-            const int rc = ldsp_resamp_reset(q->aud[c]);
-            if (rc != LDSP_OK) throw Error(rc, g_last_error);
-        }
+        for (int c = 0; c < 2; c++) ok(ldsp_resamp_reset(q->aud[c]));   // demod.hpp:34-37: only the resamplers
     });
 }
 int ldsp_fmstereo_num_outputs(ldsp_fmstereo_t q, size_t n, size_t* nout)
@@ -3915,8 +3742,7 @@ int ldsp_fmstereo_num_outputs(ldsp_fmstereo_t q, size_t n, size_t* nout)
         NONNULL(q);
         NONNULL(nout);
         size_t k = 0;
-        const int rc = ldsp_resamp_num_outputs(q->aud[0], n, &k);
-        if (rc != LDSP_OK) throw Error(rc, g_last_error);
+        ok(ldsp_resamp_num_outputs(q->aud[0], n, &k));
         *nout = 2 * k;
     });
 }
@@ -3924,11 +3750,7 @@ int ldsp_fmstereo_get_state(ldsp_fmstereo_t q, uint32_t* theta, uint32_t* dtheta
 {
     return guard([&] {
         NONNULL(q);
-        if (q->device >= 0) {
-            DeviceGuard g(q->device);
-            if (q->last) LDSP_HIP(hipStreamSynchronize(q->last));
-            LDSP_HIP(hipMemcpy(&q->st, q->dst.p, sizeof(q->st), hipMemcpyDeviceToHost));
-        }
+        q->at_rest([&] { LDSP_HIP(hipMemcpy(&q->st, q->dst.p, sizeof(q->st), hipMemcpyDeviceToHost)); });
         if (theta) *theta = q->st.theta;
         if (dtheta) *dtheta = q->st.dtheta;
         if (pe) *pe = q->st.pe;
@@ -3941,29 +3763,16 @@ int ldsp_fmstereo_execute(ldsp_fmstereo_t q, const void* x, size_t n, void* y, s
     return guard([&] {
         NONNULL(q);
         size_t k = 0;
-        int rc = ldsp_resamp_num_outputs(q->aud[0], n, &k);
-        if (rc != LDSP_OK) throw Error(rc, g_last_error);
+        ok(ldsp_resamp_num_outputs(q->aud[0], n, &k));
         if (nout) *nout = 2 * k;
         if (2 * k > cap) throw Error(LDSP_ERANGE, "fmstereo_execute: output capacity too small");
         LDSP_REQUIRE(n == 0 || x, "fmstereo_execute: NULL input");
         LDSP_REQUIRE(k == 0 || y, "fmstereo_execute: NULL output");
-        const BufDevice bd(mem, x);
-        if (q->device < 0) {
-            const int dev = current_device();
-            q->dst.ensure(sizeof(k::FmState), dev);
-            LDSP_HIP(hipMemcpy(q->dst.p, &q->st, sizeof(q->st), hipMemcpyHostToDevice));
-            upload(q->dtab, q->table, dev);
-            q->device = dev;
-        }
-        DeviceGuard g(q->device);
-        const Exec e = make_exec(q->device, mem, stream, bd);
-        q->ord.wait(e.stream);
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
         const void* dx = q->stg.dev_in(e, x, n * 8);
         float* dy = (float*)q->stg.dev_out(e, y, 2 * k * 4);
         if (n > 0) {
-            auto ok = [](int r) {
-                if (r != LDSP_OK) throw Error(r, g_last_error);
-            };
             float* sd = (float*)q->sbuf.ensure(n * 4, q->device);
             ok(ldsp_freqdem_demodulate(q->dem, dx, n, sd, LDSP_MEM_DEVICE, e.stream));
             float* l = (float*)q->lr[0].ensure(n * 4, q->device);
@@ -3980,33 +3789,8 @@ int ldsp_fmstereo_execute(ldsp_fmstereo_t q, const void* x, size_t n, void* y, s
             }
             k::interleave2(outs[0], outs[1], k, dy, e.stream);
         }
-        q->ord.mark(e.stream);
-        q->last = e.stream;
+        call.end();
         q->stg.finish(e, y, 2 * k * 4);
-    });
-}
-
-int ldsp_debug_agc_dispatch(ldsp_agc_t q, size_t n, int* path, int* W, int* Wa, int* C, long* hist_len,
-                            long* hist_valid, int* spec)
-{
-    return guard([&] {
-        NONNULL(q);
-        const AgcChoice ch = agc_choice(q, n);
-        if (path) *path = ch.path;
-        if (W) *W = ch.W;
-        if (Wa) *Wa = ch.Wa;
-        if (C) *C = ch.C;
-        if (hist_len) *hist_len = ch.hist_len;
-        if (hist_valid) *hist_valid = ch.hist_len == q->hist_len ? q->hist_valid : 0;
-        if (spec) *spec = ch.spec ? 1 : 0;
-    });
-}
-int ldsp_debug_ampmodem_dispatch(ldsp_ampmodem_t q, size_t n, int* parallel, int* batchable)
-{
-    return guard([&] {
-        NONNULL(q);
-        if (parallel) *parallel = k::pll_parallel(n, q->suppressed ? 1 : 0) ? 1 : 0;
-        if (batchable) *batchable = q->type == 0 ? 1 : 0;
     });
 }
 
@@ -4033,10 +3817,7 @@ static int run_many(T* const* q, int C, void* stream, B&& batchable, F&& one)
         bool all = true;
         for (int c = 0; c < C; c++) all = all && batchable(c);
         if (!all) {
-            for (int c = 0; c < C; c++) {
-                const int rc = one(c);
-                if (rc != LDSP_OK) throw Error(rc, g_last_error);
-            }
+            for (int c = 0; c < C; c++) ok(one(c));
             return;
         }
         BatchRecorder rec(C, (hipStream_t)stream);
@@ -4214,9 +3995,13 @@ int ldsp_bytes_to_iq(const void* in, size_t nbytes, void* y, int mem, void* stre
     return guard([&] {
         const size_t n = nbytes / 4;
         LDSP_REQUIRE(n == 0 || (in && y), "bytes_to_iq: NULL buffer");
-        const BufDevice bd(mem, in);
-        const int dev = bd.dev;
-        const Exec e = make_exec(dev, mem, stream, bd);
+        // no object: a transient one binds to the buffer's device and leaves nothing to order
+        struct Unbound : DevObj {
+            void bind(int) {}
+        } none;
+        Call call(none, mem, in, stream, false);
+        const Exec& e = call.e;
+        const int dev = e.device;
         std::unique_lock<std::mutex> lk(mu, std::defer_lock);
         if (e.host) lk.lock();   // the staging buffers are shared by host-memory calls
         if ((int)stgs.size() <= dev) stgs.resize(dev + 1);

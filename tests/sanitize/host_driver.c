@@ -4,8 +4,11 @@
  * instrumented, kernel objects as built) and run without a GPU by
  * tests/test_sanitizers.py: every designer (iirdes all prototypes x bands x
  * orders, firdes, resampler, AmpModem / FMStereo / BroadcastAM setup), every
- * property, the error paths (NULL handles, invalid designs, capacities) and the
- * execute calls that must fail cleanly with LDSP_EHIP when no device exists.
+ * property, the error paths (NULL handles, invalid designs, capacities) and
+ * every execute entry point's way into a call: with valid arguments it must
+ * fail cleanly with LDSP_EHIP when no device exists, with a `mem` that is
+ * neither LDSP_MEM_HOST nor LDSP_MEM_DEVICE with LDSP_EINVAL, and leave an
+ * object that reset and destroy take as one that was never bound.
  * Exit status 0 = every check held; the sanitizers abort on the first report. */
 #include <math.h>
 #include <stdio.h>
@@ -251,6 +254,126 @@ static void misc(void)
     CHECK(ldsp_debug_host_pools(&total, &idle) == LDSP_OK);
 }
 
+/* Every execute entry point on a machine without a device: valid arguments in
+ * host memory are LDSP_EHIP (no CPU fallback), a bad `mem` is LDSP_EINVAL, and
+ * the object stays unbound: its reset has nothing to do and its destroy nothing
+ * to wait for. */
+#define NO_DEVICE(call_host, call_bad)                                              \
+    do {                                                                            \
+        CHECK((call_host) == LDSP_EHIP && strstr(ldsp_last_error(), "no CPU fallback") != NULL); \
+        CHECK((call_bad) == LDSP_EINVAL && strstr(ldsp_last_error(), "mem") != NULL); \
+    } while (0)
+enum { BAD_MEM = 7 };
+
+static void no_device_calls(void)
+{
+    static float x[2 * 16], y[2 * 256], y1[2 * 16];
+    const size_t n = 16;
+    size_t nout = 0;
+
+    const float h5[5] = {0.1f, 0.2f, 0.4f, 0.2f, 0.1f};
+    ldsp_firfilt_t fir = NULL;
+    CHECK(ldsp_firfilt_create(h5, 5, 1, &fir) == LDSP_OK);
+    NO_DEVICE(ldsp_firfilt_execute(fir, x, n, y, LDSP_MEM_HOST, NULL), ldsp_firfilt_execute(fir, x, n, y, BAD_MEM, NULL));
+    CHECK(ldsp_firfilt_reset(fir) == LDSP_OK);
+
+    ldsp_resamp_t rs = NULL;
+    CHECK(ldsp_resamp_create(0.5f, 4, 0.2f, 60.0f, 32, 1, &rs) == LDSP_OK);
+    NO_DEVICE(ldsp_resamp_execute(rs, x, n, y, n, &nout, LDSP_MEM_HOST, NULL),
+              ldsp_resamp_execute(rs, x, n, y, n, &nout, BAD_MEM, NULL));
+    CHECK(nout > 0 && nout <= n && ldsp_resamp_reset(rs) == LDSP_OK);
+
+    ldsp_nco_t nco = NULL;
+    CHECK(ldsp_nco_create(0, &nco) == LDSP_OK && ldsp_nco_set_frequency(nco, 0.3f) == LDSP_OK);
+    NO_DEVICE(ldsp_nco_mix(nco, x, n, y, 1, LDSP_MEM_HOST, NULL), ldsp_nco_mix(nco, x, n, y, 1, BAD_MEM, NULL));
+    NO_DEVICE(ldsp_nco_mix_firfilt(nco, fir, x, n, y, 1, LDSP_MEM_HOST, NULL),
+              ldsp_nco_mix_firfilt(nco, fir, x, n, y, 1, BAD_MEM, NULL));
+    uint32_t th = 1, dth = 0;
+    CHECK(ldsp_nco_get_state(nco, &th, &dth) == LDSP_OK && th == 0);      /* no failed call advanced the phase */
+    CHECK(ldsp_nco_reset(nco) == LDSP_OK && ldsp_nco_destroy(nco) == LDSP_OK);
+    CHECK(ldsp_firfilt_destroy(fir) == LDSP_OK);
+
+    ldsp_iirfilt_t iir = NULL;
+    CHECK(ldsp_iirfilt_create_prototype(0, 0, 2, 0.1f, 0.0f, 0.5f, 60.0f, 1, &iir) == LDSP_OK);
+    NO_DEVICE(ldsp_iirfilt_execute(iir, x, n, y, LDSP_MEM_HOST, NULL), ldsp_iirfilt_execute(iir, x, n, y, BAD_MEM, NULL));
+    NO_DEVICE(ldsp_iirfilt_execute_iq16(iir, x, n, y, LDSP_MEM_HOST, NULL),
+              ldsp_iirfilt_execute_iq16(iir, x, n, y, BAD_MEM, NULL));
+    NO_DEVICE(ldsp_iirfilt_resamp_execute(iir, rs, x, n, y, n, &nout, LDSP_MEM_HOST, NULL),
+              ldsp_iirfilt_resamp_execute(iir, rs, x, n, y, n, &nout, BAD_MEM, NULL));
+    CHECK(ldsp_iirfilt_reset(iir) == LDSP_OK && ldsp_iirfilt_destroy(iir) == LDSP_OK);
+    CHECK(ldsp_resamp_reset(rs) == LDSP_OK && ldsp_resamp_destroy(rs) == LDSP_OK);
+
+    ldsp_agc_t agc = NULL;
+    CHECK(ldsp_agc_create(&agc) == LDSP_OK);
+    NO_DEVICE(ldsp_agc_execute(agc, x, n, y, NULL, LDSP_MEM_HOST, NULL), ldsp_agc_execute(agc, x, n, y, NULL, BAD_MEM, NULL));
+    CHECK(ldsp_agc_reset(agc) == LDSP_OK && ldsp_agc_destroy(agc) == LDSP_OK);
+
+    for (int type = 0; type < 3; type++) {
+        ldsp_ampmodem_t am = NULL;
+        CHECK(ldsp_ampmodem_create(0.5f, type, 0, &am) == LDSP_OK);
+        NO_DEVICE(ldsp_ampmodem_demodulate(am, x, n, y, LDSP_MEM_HOST, NULL),
+                  ldsp_ampmodem_demodulate(am, x, n, y, BAD_MEM, NULL));
+        CHECK(ldsp_ampmodem_reset(am) == LDSP_OK && ldsp_ampmodem_destroy(am) == LDSP_OK);
+    }
+
+    ldsp_bcastam_t b = NULL;
+    CHECK(ldsp_bcastam_create(25, &b) == LDSP_OK);
+    NO_DEVICE(ldsp_bcastam_demodulate(b, x, n, y, y1, LDSP_MEM_HOST, NULL),
+              ldsp_bcastam_demodulate(b, x, n, y, y1, BAD_MEM, NULL));
+    CHECK(ldsp_bcastam_reset(b) == LDSP_OK && ldsp_bcastam_destroy(b) == LDSP_OK);
+
+    ldsp_freqdem_t fd = NULL;
+    CHECK(ldsp_freqdem_create(4.0f, &fd) == LDSP_OK);
+    NO_DEVICE(ldsp_freqdem_demodulate(fd, x, n, y, LDSP_MEM_HOST, NULL), ldsp_freqdem_demodulate(fd, x, n, y, BAD_MEM, NULL));
+    CHECK(ldsp_freqdem_reset(fd) == LDSP_OK && ldsp_freqdem_destroy(fd) == LDSP_OK);
+
+    ldsp_delay_t d = NULL;
+    CHECK(ldsp_delay_create(3, &d) == LDSP_OK);
+    for (int cplx = 0; cplx < 2; cplx++)
+        NO_DEVICE(ldsp_delay_execute(d, x, n, cplx, y, LDSP_MEM_HOST, NULL),
+                  ldsp_delay_execute(d, x, n, cplx, y, BAD_MEM, NULL));
+    CHECK(ldsp_delay_set_delay(d, 5) == LDSP_OK && ldsp_delay_destroy(d) == LDSP_OK);
+
+    for (int op = LDSP_HILB_R2C; op <= LDSP_HILB_INTERP; op++) {
+        ldsp_firhilb_t hb = NULL;
+        CHECK(ldsp_firhilb_create(5, 60.0f, op, &hb) == LDSP_OK);
+        float* second = op == LDSP_HILB_C2R ? y1 : NULL;
+        NO_DEVICE(ldsp_firhilb_execute(hb, x, n, y, second, LDSP_MEM_HOST, NULL),
+                  ldsp_firhilb_execute(hb, x, n, y, second, BAD_MEM, NULL));
+        CHECK(ldsp_firhilb_reset(hb) == LDSP_OK && ldsp_firhilb_destroy(hb) == LDSP_OK);
+    }
+
+    ldsp_fmstereo_t fm = NULL;
+    CHECK(ldsp_fmstereo_create(600000.0f, 48000.0f, &fm) == LDSP_OK);
+    NO_DEVICE(ldsp_fmstereo_execute(fm, x, n, y, 64, &nout, LDSP_MEM_HOST, NULL),
+              ldsp_fmstereo_execute(fm, x, n, y, 64, &nout, BAD_MEM, NULL));
+    uint32_t fth = 1, fdth = 1;
+    float pe = 1.0f;
+    CHECK(ldsp_fmstereo_get_state(fm, &fth, &fdth, &pe) == LDSP_OK && fth == 0 && fdth == 0 && pe == 0.0f);
+    CHECK(ldsp_fmstereo_reset(fm) == LDSP_OK && ldsp_fmstereo_destroy(fm) == LDSP_OK);
+
+    for (unsigned ld = 4; ld <= 6; ld += 2) {                  /* dense rows and rows ld apart */
+        ldsp_chan_t ch = NULL;
+        size_t ncols = 0;
+        CHECK(ldsp_chan_create(4, 4, 2, 0.0f, 60.0f, &ch) == LDSP_OK);
+        NO_DEVICE(ldsp_chan_execute(ch, x, n, y, ld, &ncols, LDSP_MEM_HOST, NULL),
+                  ldsp_chan_execute(ch, x, n, y, ld, &ncols, BAD_MEM, NULL));
+        CHECK(ncols == 4 && ldsp_chan_reset(ch) == LDSP_OK && ldsp_chan_destroy(ch) == LDSP_OK);
+    }
+
+    ldsp_spgram_t sp = NULL;
+    size_t nrows = 9;
+    double psd[256];
+    uint64_t nt = 9;
+    CHECK(ldsp_spgram_create(256, LDSP_WIN_HANN, 256, 128, 1, &sp) == LDSP_OK);
+    NO_DEVICE(ldsp_spgram_execute(sp, x, n, y, 256, &nrows, LDSP_MEM_HOST, NULL),
+              ldsp_spgram_execute(sp, x, n, y, 256, &nrows, BAD_MEM, NULL));
+    CHECK(nrows == 0 && ldsp_spgram_get_psd(sp, psd, &nt) == LDSP_OK && nt == 0 && psd[0] == 0.0);
+    CHECK(ldsp_spgram_clear(sp) == LDSP_OK && ldsp_spgram_reset(sp) == LDSP_OK && ldsp_spgram_destroy(sp) == LDSP_OK);
+
+    NO_DEVICE(ldsp_bytes_to_iq(x, 4 * n, y, LDSP_MEM_HOST, NULL), ldsp_bytes_to_iq(x, 4 * n, y, BAD_MEM, NULL));
+}
+
 int main(void)
 {
     misc();
@@ -258,6 +381,7 @@ int main(void)
     fir_designs();
     resamplers();
     loops();
+    no_device_calls();
     if (fails) {
         fprintf(stderr, "%d checks failed\n", fails);
         return 1;

@@ -126,6 +126,9 @@ static void user_taps_and_execute_errors(int ndev)
     CHECK(ldsp_synth_execute(q, NULL, 16, 16, z, 64, &n, LDSP_MEM_HOST, NULL) == LDSP_EINVAL);
     CHECK(ldsp_synth_execute(q, y, 16, 16, NULL, 64, &n, LDSP_MEM_HOST, NULL) == LDSP_EINVAL);
     CHECK(ldsp_synth_execute(q, y, 16, 16, z, 64, &n, 7, NULL) == LDSP_EINVAL);
+    CHECK(strstr(ldsp_last_error(), "mem") != NULL);
+    /* the same with rows ld > ncols apart: still decided before the image is touched */
+    CHECK(ldsp_synth_execute(q, y, 20, 16, z, 64, &n, 7, NULL) == LDSP_EINVAL && n == 64);
     if (ndev == 0) {                                     /* valid arguments: no device, no CPU fallback */
         CHECK(ldsp_synth_execute(q, y, 16, 16, z, 64, &n, LDSP_MEM_HOST, NULL) == LDSP_EHIP);
         CHECK(strstr(ldsp_last_error(), "no CPU fallback") != NULL);

@@ -200,6 +200,90 @@ def test_execute_without_gpu_fails_loudly(lib):
     lib.ldsp_agc_destroy(a)
 
 
+def _f(v):
+    return C.c_float(v)
+
+
+def _make(lib, what):
+    """A small valid object of class `what`; returns (handle, destroy)."""
+    q = C.c_void_p()
+    if what == "firfilt":       # 5 taps, complex
+        h = np.array([0.1, 0.2, 0.4, 0.2, 0.1], np.float32)
+        rc = lib.ldsp_firfilt_create(ptr(h), 5, 1, C.byref(q))
+    elif what == "resamp":      # rate 0.5, m = 4, complex
+        rc = lib.ldsp_resamp_create(_f(0.5), 4, _f(0.2), _f(60.0), 32, 1, C.byref(q))
+    elif what == "nco":
+        rc = lib.ldsp_nco_create(0, C.byref(q))
+    elif what == "iirfilt":     # order 2 Butterworth lowpass, complex
+        rc = lib.ldsp_iirfilt_create_prototype(0, 0, 2, _f(0.1), _f(0.0), _f(0.5), _f(60.0), 1, C.byref(q))
+    elif what == "agc":
+        rc = lib.ldsp_agc_create(C.byref(q))
+    elif what == "ampmodem":
+        rc = lib.ldsp_ampmodem_create(_f(0.5), 0, 0, C.byref(q))
+    elif what == "bcastam":
+        rc = lib.ldsp_bcastam_create(25, C.byref(q))
+    elif what == "freqdem":
+        rc = lib.ldsp_freqdem_create(_f(4.0), C.byref(q))
+    elif what == "delay":
+        rc = lib.ldsp_delay_create(3, C.byref(q))
+    elif what == "firhilb":     # LDSP_HILB_R2C
+        rc = lib.ldsp_firhilb_create(5, _f(60.0), 0, C.byref(q))
+    else:
+        assert what == "fmstereo"
+        rc = lib.ldsp_fmstereo_create(_f(600000.0), _f(48000.0), C.byref(q))
+    assert rc == 0 and q.value, lib.ldsp_last_error()
+    return q, getattr(lib, "ldsp_%s_destroy" % what)
+
+
+# entry point -> (the classes of its objects, the call given the handles, buffers and `mem`)
+BAD_MEM_CASES = {
+    "ldsp_firfilt_execute": (["firfilt"], lambda L, q, x, y, n, no, m: L.ldsp_firfilt_execute(q[0], x, n, y, m, None)),
+    "ldsp_resamp_execute": (["resamp"],
+                            lambda L, q, x, y, n, no, m: L.ldsp_resamp_execute(q[0], x, n, y, n, no, m, None)),
+    "ldsp_nco_mix": (["nco"], lambda L, q, x, y, n, no, m: L.ldsp_nco_mix(q[0], x, n, y, 1, m, None)),
+    "ldsp_nco_mix_firfilt": (["nco", "firfilt"],
+                             lambda L, q, x, y, n, no, m: L.ldsp_nco_mix_firfilt(q[0], q[1], x, n, y, 1, m, None)),
+    "ldsp_iirfilt_execute": (["iirfilt"], lambda L, q, x, y, n, no, m: L.ldsp_iirfilt_execute(q[0], x, n, y, m, None)),
+    "ldsp_iirfilt_execute_iq16": (["iirfilt"],
+                                  lambda L, q, x, y, n, no, m: L.ldsp_iirfilt_execute_iq16(q[0], x, n, y, m, None)),
+    "ldsp_iirfilt_resamp_execute": (["iirfilt", "resamp"],
+                                    lambda L, q, x, y, n, no, m: L.ldsp_iirfilt_resamp_execute(q[0], q[1], x, n, y, n,
+                                                                                               no, m, None)),
+    "ldsp_agc_execute": (["agc"], lambda L, q, x, y, n, no, m: L.ldsp_agc_execute(q[0], x, n, y, None, m, None)),
+    "ldsp_ampmodem_demodulate": (["ampmodem"],
+                                 lambda L, q, x, y, n, no, m: L.ldsp_ampmodem_demodulate(q[0], x, n, y, m, None)),
+    "ldsp_bcastam_demodulate": (["bcastam"],
+                                lambda L, q, x, y, n, no, m: L.ldsp_bcastam_demodulate(q[0], x, n, y, None, m, None)),
+    "ldsp_freqdem_demodulate": (["freqdem"],
+                                lambda L, q, x, y, n, no, m: L.ldsp_freqdem_demodulate(q[0], x, n, y, m, None)),
+    "ldsp_delay_execute": (["delay"], lambda L, q, x, y, n, no, m: L.ldsp_delay_execute(q[0], x, n, 1, y, m, None)),
+    "ldsp_firhilb_execute": (["firhilb"],
+                             lambda L, q, x, y, n, no, m: L.ldsp_firhilb_execute(q[0], x, n, y, None, m, None)),
+    "ldsp_fmstereo_execute": (["fmstereo"],
+                              lambda L, q, x, y, n, no, m: L.ldsp_fmstereo_execute(q[0], x, n, y, C.c_size_t(64), no, m,
+                                                                                   None)),
+}
+
+
+@pytest.mark.parametrize("entry", sorted(BAD_MEM_CASES))
+def test_bad_mem_is_einval_before_any_device_work(lib, entry):
+    """A `mem` that is neither LDSP_MEM_HOST nor LDSP_MEM_DEVICE is LDSP_EINVAL
+    from every execute entry point, decided before any HIP call: the same code
+    with and without a GPU, nothing bound, nothing launched (16 samples, valid
+    objects and buffers)."""
+    classes, call = BAD_MEM_CASES[entry]
+    made = [_make(lib, w) for w in classes]
+    x = np.zeros(16, np.complex64)         # 16 complex samples (or 16 int16 IQ pairs, or 16 floats) fit
+    y = np.zeros(64, np.complex64)
+    nout = C.c_size_t(0)
+    rc = call(lib, [q for q, _ in made], ptr(x), ptr(y), C.c_size_t(16), C.byref(nout), 7)
+    err = lib.ldsp_last_error()
+    for q, destroy in made:
+        assert destroy(q) == 0
+    assert rc == LDSP_EINVAL, (rc, err)
+    assert b"mem" in err
+
+
 # ------------------------------------------------------------------ pybind11 module surface
 @pytest.fixture(scope="module")
 def ld():
