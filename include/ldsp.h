@@ -593,6 +593,65 @@ int ldsp_synth_execute(ldsp_synth_t q, const void *y, size_t ld, size_t ncols, v
 int ldsp_debug_synth_tile(unsigned int M, unsigned int D, size_t *cols);
 
 /* ------------------------------------------------------------------------
+ * Downconverter: a bank of C independently tuned decimating filters ("tune,
+ * low-pass, decimate") over one wideband complex64 stream, read once.
+ * liquid's counterpart is nco_crcf + firdecim_crcf; the definition is this
+ * library's own.  For the concatenated input x[t] (t counted from 0 since
+ * creation or reset, zeros before it), a real prototype h of L taps, a
+ * decimation D and tuners c < C with 32-bit frequency words w_c:
+ *   phase(c, t) = (t w_c) mod 2^32                       (integers, exact for any t)
+ *   y[c][n]     = scale sum_{j<L} h[j] x[nD - j] exp(-2 pi i phase(c, nD - j) / 2^32)
+ * w_c = rint(f_c 2^32) mod 2^32 for a frequency f_c in cycles per sample (a
+ * finite double, |f_c| <= 1; the product is exact, ties go to even); the
+ * tuner's true frequency is w_c / 2^32.  The sum is evaluated as
+ *   g_c[j]   = h[j] exp(+2 pi i ((j w_c) mod 2^32) / 2^32)        (double, rounded once)
+ *   y[c][n]  = scale rot_c(n) sum_j g_c[j] x[nD - j]
+ *   rot_c(n) = exp(-2 pi i (((nD) mod 2^32) w_c mod 2^32) / 2^32)
+ * which is the same sum, the phase being additive modulo 2^32.  The column
+ * schedule is the Channelizer's: output n is emitted by the call that delivers
+ * x[nD]; with T samples seen before a call and skip = (-T) mod D, a call of n
+ * samples returns n > skip ? ceil((n - skip) / D) : 0 columns; calls of any
+ * length, 0 included, are allowed.  A row's bits depend neither on how the
+ * stream is cut into calls nor on the other tuners, their number or order.
+ *   2 <= D <= 256, any integer;  1 <= C <= 64;  1 <= L <= 17 D;  1 <= m <= 8.
+ * ldsp_ddc_create designs h = firdes_kaiser(2 D m + 1, fc, as, 0) (fc <= 0:
+ * 0.5 / D) and sets scale = 1 / sum(h); ldsp_ddc_create_taps takes h as given
+ * with scale = 1.  D = 0, C = 0, L = 0, m = 0, as <= 0, fc >= 0.5, a NULL f and
+ * an f_c that is not finite or above 1 in magnitude are LDSP_EINVAL; D = 1
+ * (ldsp_nco_mix_firfilt serves it), D > 256, C > 64, L > 17 D and m > 8 are
+ * LDSP_EUNSUP.  ldsp_ddc_set_frequencies retunes (C may change): the history
+ * holds raw input, so the following columns are those of a bank created with
+ * the new list and fed the same stream in the same cuts.  ldsp_ddc_execute
+ * writes row c to y + c * ld (ld in samples); it sets *ncols and, when
+ * ld < *ncols, returns LDSP_ERANGE without consuming the input.  Argument
+ * errors are decided on the host before any device work.
+ * Not built: D = 1, real input, per-tuner prototypes or decimations, a
+ * fast-convolution (FFT) form.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_ddc_s *ldsp_ddc_t;
+int ldsp_ddc_create(const double *f, unsigned int C, unsigned int D, unsigned int m, float fc, float as,
+                    ldsp_ddc_t *q);
+int ldsp_ddc_create_taps(const double *f, unsigned int C, unsigned int D, const float *h, unsigned int L,
+                         ldsp_ddc_t *q);
+int ldsp_ddc_destroy(ldsp_ddc_t q);
+int ldsp_ddc_reset(ldsp_ddc_t q);
+int ldsp_ddc_set_frequencies(ldsp_ddc_t q, const double *f, unsigned int C);   /* C may change, 1..64 */
+int ldsp_ddc_get_words(ldsp_ddc_t q, uint32_t *w);                             /* C words */
+/* Any pointer may be NULL.  skip: input samples before the next call's first output. */
+int ldsp_ddc_get_info(ldsp_ddc_t q, unsigned int *C, unsigned int *D, unsigned int *L, unsigned int *skip);
+int ldsp_ddc_get_taps(ldsp_ddc_t q, float *h);                   /* L floats */
+int ldsp_ddc_get_scale(ldsp_ddc_t q, float *s);
+int ldsp_ddc_set_scale(ldsp_ddc_t q, float s);
+int ldsp_ddc_num_outputs(ldsp_ddc_t q, size_t n, size_t *ncols);
+int ldsp_ddc_execute(ldsp_ddc_t q, const void *x, size_t n, void *y, size_t ld, size_t *ncols, int mem,
+                     void *stream);
+/* Test hook: output columns per workgroup of the (D, L) kernel. */
+int ldsp_debug_ddc_tile(unsigned int D, unsigned int L, size_t *frames);
+/* Test hook: reset, then place the stream at sample T (zero history), to reach
+ * the phase arithmetic near T = 2^32 without streaming that far. */
+int ldsp_debug_ddc_seek(ldsp_ddc_t q, uint64_t T);
+
+/* ------------------------------------------------------------------------
  * Spectrogram: a streaming Welch periodogram, one complex64 stream to rows of
  * power per bin and a running mean of them.  No reference counterpart
  * (liquid's spgramcf / spwaterfallcf are the same block: a zeroed window

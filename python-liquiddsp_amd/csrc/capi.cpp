@@ -1291,6 +1291,53 @@ struct ldsp_chan_s : BankObj {
 // from the columns seen; the history is the last Q - 1 input columns as [M][Q - 1].
 struct ldsp_synth_s : BankObj {};
 
+// Downconverter (tuned decimating bank): the prototype, the frequency words,
+// the host-side stream position (skip and the first column's absolute index
+// follow from it), and on the device the complex taps g_c in the kernel's
+// layout (kernels.hpp), the words and the last L - 1 raw input samples,
+// ping-ponged.  The history is raw input, so a retune touches the tables alone.
+struct ldsp_ddc_s : ldsp::DevObj {
+    unsigned int D = 0;
+    std::vector<float> h;
+    std::vector<uint32_t> w;
+    float scale = 1.0f;
+    uint64_t seen = 0;                     // input samples since create / reset (or the seek hook's T)
+    ldsp::DevBuf dtaps, dwords, dslots;
+    ldsp::PingPong hist;
+    size_t hist_bytes() const { return std::max<size_t>(h.size() - 1, 1) * 8; }
+    size_t skip() const { return (size_t)((D - seen % D) % D); }
+    size_t num_outputs(size_t n) const { return n > skip() ? (n - skip() + D - 1) / D : 0; }
+    uint64_t next_column() const { return seen / D + (seen % D != 0); }
+    // g_c[j] = h[j] exp(+2 pi i ((j w_c) mod 2^32) / 2^32) in double, rounded once, as
+    // [tuner block][k = L - 1 - j][TB]; the phase as a signed count of 2^-31 half-turns
+    void upload_tables(int dev)
+    {
+        const size_t C = w.size(), L = h.size();
+        const size_t TB = (size_t)ldsp::k::ddc_block((int)C), nb = (C + TB - 1) / TB;
+        std::vector<float> g(2 * nb * L * TB, 0.0f);
+        for (size_t c = 0; c < C; c++)
+            for (size_t j = 0; j < L; j++) {
+                const uint32_t ph = (uint32_t)j * w[c];
+                const double a = M_PI * ((double)(int32_t)ph / 2147483648.0);
+                const size_t at = ((c / TB * L + (L - 1 - j)) * TB + c % TB) * 2;
+                g[at] = (float)((double)h[j] * cos(a));
+                g[at + 1] = (float)((double)h[j] * sin(a));
+            }
+        ldsp::upload(dtaps, g, dev);
+        std::vector<uint32_t> wp(w);
+        wp.resize(nb * TB, 0u);
+        ldsp::upload(dwords, wp, dev);
+    }
+    void bind(int dev)
+    {
+        upload_tables(dev);
+        std::vector<int> slots(h.size());
+        for (size_t k = 0; k < slots.size(); k++) slots[k] = ldsp::k::ddc_slot((int)D, (int)h.size(), (int)k);
+        ldsp::upload(dslots, slots, dev);
+        hist.zero(hist_bytes(), dev);
+    }
+};
+
 // Spectrogram (streaming Welch periodogram): the window, the host-side counts
 // (samples since reset, transforms since clear; the schedule follows from
 // them), and on the device the padded window, the twiddle table, the last
@@ -3478,6 +3525,183 @@ int ldsp_debug_synth_tile(unsigned int M, unsigned int D, size_t* cols)
         bank_check_shape(kSynth, M, D);
         bank_check_channels(kSynth, M);
         *cols = (size_t)k::synth_cols((int)M);
+    });
+}
+
+// ---------------------------------------------------------------- Downconverter
+// w = rint(f 2^32) mod 2^32: the product is exact (a power of two), rint rounds ties to even
+static std::vector<uint32_t> ddc_words(const double* f, unsigned int C)
+{
+    LDSP_REQUIRE(C >= 1, "ddc: at least one tuner");
+    if (C > (unsigned)k::kDdcMaxC)
+        throw Error(LDSP_EUNSUP, "ddc: more than " + std::to_string(k::kDdcMaxC) + " tuners is not implemented");
+    LDSP_REQUIRE(f != nullptr, "f must not be NULL");
+    std::vector<uint32_t> w(C);
+    for (unsigned c = 0; c < C; c++) {
+        LDSP_REQUIRE(std::isfinite(f[c]) && std::fabs(f[c]) <= 1.0,
+                     "ddc: a frequency must be finite and at most 1 cycle per sample in magnitude");
+        w[c] = (uint32_t)(uint64_t)(int64_t)std::nearbyint(f[c] * 4294967296.0);
+    }
+    return w;
+}
+static void ddc_check_decim(unsigned int D)
+{
+    LDSP_REQUIRE(D >= 1, "ddc: the decimation must be at least 2");
+    if (D == 1) throw Error(LDSP_EUNSUP, "ddc: decimation 1 is not implemented (mix_down_filter serves it)");
+    if (D > (unsigned)k::kDdcMaxD)
+        throw Error(LDSP_EUNSUP, "ddc: decimation above " + std::to_string(k::kDdcMaxD) + " is not implemented");
+}
+static ldsp_ddc_s* ddc_make(std::vector<uint32_t> w, unsigned int D, std::vector<float> h, float scale)
+{
+    if (h.size() > (size_t)k::kChanMaxP * D)
+        throw Error(LDSP_EUNSUP, "ddc: more than " + std::to_string(k::kChanMaxP) + " taps per output phase (L > " +
+                                     std::to_string(k::kChanMaxP) + " D) is not implemented");
+    std::unique_ptr<ldsp_ddc_s> o(new ldsp_ddc_s());
+    o->D = D;
+    o->h = std::move(h);
+    o->w = std::move(w);
+    o->scale = scale;
+    return o.release();
+}
+int ldsp_ddc_create(const double* f, unsigned int C, unsigned int D, unsigned int m, float fc, float as, ldsp_ddc_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        ddc_check_decim(D);
+        std::vector<uint32_t> w = ddc_words(f, C);
+        LDSP_REQUIRE(m >= 1, "ddc: filter semi-length must be at least 1");
+        LDSP_REQUIRE(as > 0.0f, "ddc: stop-band attenuation must be > 0");
+        LDSP_REQUIRE(fc < 0.5f, "ddc: cutoff must be below 0.5");
+        if (2 * (size_t)m + 1 > (size_t)k::kChanMaxP)
+            throw Error(LDSP_EUNSUP, "ddc: semi-length above " + std::to_string((k::kChanMaxP - 1) / 2) +
+                                         " is not implemented");
+        std::vector<float> h = design::firdes_kaiser(2 * D * m + 1, fc > 0.0f ? fc : 0.5f / (float)D, as, 0.0f);
+        double sum = 0.0;
+        for (float v : h) sum += (double)v;
+        *q = ddc_make(std::move(w), D, std::move(h), (float)(1.0 / sum));
+    });
+}
+int ldsp_ddc_create_taps(const double* f, unsigned int C, unsigned int D, const float* h, unsigned int L, ldsp_ddc_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        ddc_check_decim(D);
+        std::vector<uint32_t> w = ddc_words(f, C);
+        LDSP_REQUIRE(L >= 1, "ddc: at least one tap");
+        NONNULL(h);
+        *q = ddc_make(std::move(w), D, std::vector<float>(h, h + L), 1.0f);
+    });
+}
+int ldsp_ddc_destroy(ldsp_ddc_t q) { return guard([&] { destroy(q); }); }
+static void ddc_restart(ldsp_ddc_t q, uint64_t T)
+{
+    q->seen = T;
+    q->at_rest([&] { q->hist.zero(q->hist_bytes(), q->device); });
+}
+int ldsp_ddc_reset(ldsp_ddc_t q) { return guard([&] { NONNULL(q); ddc_restart(q, 0); }); }
+int ldsp_debug_ddc_seek(ldsp_ddc_t q, uint64_t T) { return guard([&] { NONNULL(q); ddc_restart(q, T); }); }
+int ldsp_ddc_set_frequencies(ldsp_ddc_t q, const double* f, unsigned int C)
+{
+    return guard([&] {
+        NONNULL(q);
+        std::vector<uint32_t> w = ddc_words(f, C);
+        // the tables change only once the object's earlier calls have finished with them
+        std::swap(q->w, w);
+        try {
+            q->at_rest([&] { q->upload_tables(q->device); });
+        } catch (...) {
+            std::swap(q->w, w);
+            throw;
+        }
+    });
+}
+int ldsp_ddc_get_words(ldsp_ddc_t q, uint32_t* w)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(w);
+        std::copy(q->w.begin(), q->w.end(), w);
+    });
+}
+int ldsp_ddc_get_info(ldsp_ddc_t q, unsigned int* C, unsigned int* D, unsigned int* L, unsigned int* skip)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (C) *C = (unsigned)q->w.size();
+        if (D) *D = q->D;
+        if (L) *L = (unsigned)q->h.size();
+        if (skip) *skip = (unsigned)q->skip();
+    });
+}
+int ldsp_ddc_get_taps(ldsp_ddc_t q, float* h)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(h);
+        std::copy(q->h.begin(), q->h.end(), h);
+    });
+}
+int ldsp_ddc_get_scale(ldsp_ddc_t q, float* s) { return guard([&] { NONNULL(q); NONNULL(s); *s = q->scale; }); }
+int ldsp_ddc_set_scale(ldsp_ddc_t q, float s) { return guard([&] { NONNULL(q); q->scale = s; }); }
+int ldsp_ddc_num_outputs(ldsp_ddc_t q, size_t n, size_t* ncols)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(ncols);
+        *ncols = q->num_outputs(n);
+    });
+}
+int ldsp_ddc_execute(ldsp_ddc_t q, const void* x, size_t n, void* y, size_t ld, size_t* ncols, int mem, void* stream)
+{
+    LDSP_RANGE("ldsp_ddc_execute");
+    return guard([&] {
+        NONNULL(q);
+        const size_t K = q->num_outputs(n);
+        if (ncols) *ncols = K;
+        if (K > ld) throw Error(LDSP_ERANGE, "ddc_execute: row stride below the number of output columns");
+        LDSP_REQUIRE(n == 0 || x, "ddc_execute: NULL input");
+        LDSP_REQUIRE(K == 0 || y, "ddc_execute: NULL output");
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
+        const size_t C = q->w.size();
+        // a host-memory call computes into a dense [C][K] device image
+        // (rows of the caller's image are ld samples apart)
+        const size_t dld = e.host ? K : ld;
+        const void* dx = q->stg.dev_in(e, x, n * 8);
+        void* dy = q->stg.dev_out(e, y, C * K * 8);
+        if (n > 0) {
+            k::DdcCall c;
+            c.x = dx;
+            c.hist = q->hist.in();
+            c.hist_out = q->hist.out();
+            c.n = n;
+            c.skip = q->skip();
+            c.ncols = K;
+            c.ld = dld;
+            c.col0 = q->next_column();
+            c.C = (int)C;
+            c.L = (int)q->h.size();
+            c.taps = q->dtaps.p;
+            c.slots = q->dslots.as<int>();
+            c.words = q->dwords.as<uint32_t>();
+            c.scale = q->scale;
+            c.y = dy;
+            k::ddc((int)q->D, c, e.stream);
+            q->hist.flip();
+            q->seen += n;
+        }
+        call.end();
+        q->stg.finish(e, y, K * 8, C, ld * 8);
+    });
+}
+int ldsp_debug_ddc_tile(unsigned int D, unsigned int L, size_t* frames)
+{
+    return guard([&] {
+        NONNULL(frames);
+        ddc_check_decim(D);
+        LDSP_REQUIRE(L >= 1, "ddc: at least one tap");
+        if (L > (unsigned)k::kChanMaxP * D) throw Error(LDSP_EUNSUP, "ddc: more than 17 taps per output phase is not implemented");
+        *frames = (size_t)k::ddc_frames((int)D, (int)L);
     });
 }
 

@@ -400,6 +400,37 @@ struct ChanCall {
     void* y;
 };
 void chan(int M, int D, const ChanCall& c, hipStream_t s);
+// k_ddc.hip: tuned decimating filter bank (Downconverter).  C <= kDdcMaxC tuners,
+// decimation 2 <= D <= kDdcMaxD, one real prototype of L <= kChanMaxP D taps.
+// x: n complex64 samples; hist / hist_out: the L - 1 raw samples before x[0] /
+// before the next call's x[0], distinct buffers (at least one readable sample
+// when L = 1).  The call's columns are at x[skip + c D], c < ncols as k_chan's;
+// col0: the absolute index of the first (the rotation's phase).  With
+// TB = ddc_block(C) tuners per block, taps holds the complex taps
+// g_c[j] = h[j] exp(+2 pi i ((j w_c) mod 2^32) / 2^32) as
+// [ceil(C / TB)][L][TB] (re, im) pairs indexed by k = L - 1 - j, zero for the
+// tuners past C, words the C frequency words (padded likewise) and slots the L
+// LDS slots ddc_slot(D, L, k).  y[c * ld + col] receives tuner c.  n = 0
+// launches nothing.
+constexpr int kDdcMaxC = 64;
+constexpr int kDdcMaxD = 256;
+constexpr int ddc_block(int C) { return C >= 3 ? 4 : C; }   // tuners a wave carries at once
+int ddc_frames(int D, int L);                               // output columns per workgroup
+int ddc_slot(int D, int L, int k);                          // where the staged span keeps offset k of column 0
+struct DdcCall {
+    const void* x;
+    const void* hist;
+    void* hist_out;
+    size_t n, skip, ncols, ld;
+    uint64_t col0;
+    int C, L;
+    const void* taps;
+    const int* slots;
+    const uint32_t* words;
+    float scale;
+    void* y;
+};
+void ddc(int D, const DdcCall& c, hipStream_t s);
 // k_synth.hip: polyphase synthesis filter bank (Synthesizer), k_chan's
 // counterpart.  M rows (a power of two, 4 .. 256), interpolation D = M or M / 2,
 // Q = ceil(L / D) <= synth_qmax(M, D) taps per output residue.  y: row k at

@@ -1009,6 +1009,130 @@ struct Channelizer {
     }
 };
 
+// ------------------------------------------------------------------ Downconverter (liquid: nco_crcf + firdecim_crcf)
+// Tuned decimating bank (ldsp.h): complex64[N] -> complex64[ntuners, ncols],
+// row c the stream mixed down by freqs[c], low-passed and decimated.  The rows
+// of a device result are contiguous views, as the Channelizer's.
+struct Downconverter {
+    ldsp_ddc_t q = nullptr;
+    unsigned D = 0, L = 0;
+    static std::vector<double> to_freqs(const py::object& f)
+    {
+        if (!py::hasattr(f, "__len__")) return {f.cast<double>()};       // a scalar: one tuner
+        return f.cast<std::vector<double>>();
+    }
+    Downconverter(const py::object& freqs, int decim, int m, const py::object& fc, float as, const py::object& taps)
+    {
+        if (decim < 0) throw py::value_error("Downconverter: decim must be at least 2");
+        const std::vector<double> f = to_freqs(freqs);
+        if (!taps.is_none()) {
+            std::vector<float> h = to_fvec(taps);
+            check(ldsp_ddc_create_taps(f.data(), (unsigned)f.size(), (unsigned)decim, h.data(), (unsigned)h.size(), &q));
+        } else {
+            if (m < 0) throw py::value_error("Downconverter: m must be >= 1");
+            float c = 0.0f;                                   // the C ABI's default: 0.5 / decim
+            if (!fc.is_none()) {
+                c = fc.cast<float>();
+                if (!(c > 0.0f && c < 0.5f)) throw py::value_error("Downconverter: Fc must lie in (0, 0.5)");
+            }
+            check(ldsp_ddc_create(f.data(), (unsigned)f.size(), (unsigned)decim, (unsigned)m, c, as, &q));
+        }
+        check(ldsp_ddc_get_info(q, nullptr, &D, &L, nullptr));
+    }
+    Downconverter(const Downconverter&) = delete;
+    ~Downconverter()
+    {
+        if (q) ldsp_ddc_destroy(q);
+    }
+    void reset() { check(ldsp_ddc_reset(q)); }
+    unsigned ntuners()
+    {
+        unsigned c;
+        check(ldsp_ddc_get_info(q, &c, nullptr, nullptr, nullptr));
+        return c;
+    }
+    py::array_t<uint32_t> words()
+    {
+        py::array_t<uint32_t> w(ntuners());
+        check(ldsp_ddc_get_words(q, w.mutable_data()));
+        return w;
+    }
+    py::array_t<double> get_freqs()
+    {
+        py::array_t<uint32_t> w = words();
+        py::array_t<double> f(w.size());
+        for (py::ssize_t c = 0; c < w.size(); c++) f.mutable_at(c) = (double)(int32_t)w.at(c) / 4294967296.0;
+        return f;
+    }
+    void set_freqs(const py::object& freqs)
+    {
+        const std::vector<double> f = to_freqs(freqs);
+        check(ldsp_ddc_set_frequencies(q, f.data(), (unsigned)f.size()));
+    }
+    py::array_t<float> taps()
+    {
+        py::array_t<float> h(L);
+        check(ldsp_ddc_get_taps(q, h.mutable_data()));
+        return h;
+    }
+    float get_scale()
+    {
+        float s;
+        check(ldsp_ddc_get_scale(q, &s));
+        return s;
+    }
+    void set_scale(float s) { check(ldsp_ddc_set_scale(q, s)); }
+    unsigned skip()
+    {
+        unsigned s;
+        check(ldsp_ddc_get_info(q, nullptr, nullptr, nullptr, &s));
+        return s;
+    }
+    size_t tile()
+    {
+        size_t f = 0;
+        check(ldsp_debug_ddc_tile(D, L, &f));
+        return f;
+    }
+    size_t num_outputs(size_t n)
+    {
+        size_t c = 0;
+        check(ldsp_ddc_num_outputs(q, n, &c));
+        return c;
+    }
+    void seek(uint64_t T) { check(ldsp_debug_ddc_seek(q, T)); }
+    py::object call(const py::handle& x)
+    {
+        size_t nw = 0;
+        const unsigned C = ntuners();
+        if (is_device_tensor(x)) {
+            DevIn d = dev_in(x, true);
+            const size_t K = num_outputs(d.n);
+            py::object& torch = torch_mod();
+            py::dict kw;
+            kw["dtype"] = torch.attr("complex64");
+            kw["device"] = d.device;
+            py::object out = torch.attr("empty")(py::make_tuple(C, K), **kw);
+            check(ldsp_ddc_execute(q, d.ptr, d.n, tptr(out), K, &nw, LDSP_MEM_DEVICE, d.stream));
+            return out;
+        }
+        carr a = carr::ensure(x);
+        if (!a) throw py::error_already_set();
+        const size_t n = (size_t)a.size();
+        const size_t K = num_outputs(n);
+        py::array_t<cf> out({(py::ssize_t)C, (py::ssize_t)K});
+        void* yp = out.mutable_data();
+        const void* xp = a.data();
+        int rc;
+        {
+            py::gil_scoped_release rel;
+            rc = ldsp_ddc_execute(q, xp, n, yp, K, &nw, LDSP_MEM_HOST, nullptr);
+        }
+        check(rc);
+        return out;
+    }
+};
+
 // ------------------------------------------------------------------ Synthesizer (no reference counterpart)
 // Polyphase synthesis bank (ldsp.h): complex64[nchan, K] -> complex64[K * interp],
 // row k mixed up to k / nchan.  A device tensor whose columns are contiguous (a
@@ -1859,6 +1983,25 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def_property_readonly("tile", &Channelizer::tile, "output columns per workgroup of the kernel")
         .def_property_readonly("centers", &Channelizer::centers, "channel centres k / nchan wrapped into [-0.5, 0.5)")
         .def("__call__", &Channelizer::call, "complex64[N] -> complex64[nchan, ncols]");
+
+    // ---- Downconverter (liquid: nco_crcf + firdecim_crcf as one bank)
+    py::class_<Downconverter>(m, "Downconverter")
+        .def(py::init<py::object, int, int, py::object, float, py::object>(), py::arg("freqs"), py::arg("decim"),
+             py::arg("m") = 6, py::arg("Fc") = py::none(), py::arg("As") = 60.0f, py::arg("taps") = py::none())
+        .def("reset", &Downconverter::reset)
+        .def("num_outputs", &Downconverter::num_outputs, py::arg("n"),
+             "columns the next call returns for n input samples")
+        .def("_seek", &Downconverter::seek, py::arg("T"), "test hook: reset, then stream position T (zero history)")
+        .def_property_readonly("ntuners", &Downconverter::ntuners)
+        .def_property_readonly("decim", [](Downconverter& c) { return c.D; })
+        .def_property("freqs", &Downconverter::get_freqs, &Downconverter::set_freqs,
+                      "tuner frequencies words / 2**32 wrapped into [-0.5, 0.5); setting retunes (the count may change)")
+        .def_property_readonly("words", &Downconverter::words, "the 32-bit frequency words")
+        .def_property_readonly("taps", &Downconverter::taps)
+        .def_property("scale", &Downconverter::get_scale, &Downconverter::set_scale)
+        .def_property_readonly("skip", &Downconverter::skip, "input samples before the next call's first output")
+        .def_property_readonly("tile", &Downconverter::tile, "output columns per workgroup of the kernel")
+        .def("__call__", &Downconverter::call, "complex64[N] -> complex64[ntuners, ncols]");
 
     // ---- Synthesizer (beyond the reference: polyphase synthesis filter bank)
     py::class_<Synthesizer>(m, "Synthesizer")
