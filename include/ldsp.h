@@ -652,6 +652,56 @@ int ldsp_debug_ddc_tile(unsigned int D, unsigned int L, size_t *frames);
 int ldsp_debug_ddc_seek(ldsp_ddc_t q, uint64_t T);
 
 /* ------------------------------------------------------------------------
+ * FMBank: for every row of a complex64 [C][K] block (a Channelizer or
+ * Downconverter output, read in place), FreqDem's discriminator followed by a
+ * real decimating FIR, in one pass; the full-rate discriminator output stays
+ * on the chip.  liquid's counterpart is freqdem + firdecim_rrrf per row; the
+ * definition is this library's own.  For row c of the concatenated input
+ * x[c][t] (t counted from 0 since creation or reset; the sample before t = 0
+ * is 0, as after freqdem_reset), ref = (float)(1 / (2 pi kf)) computed as in
+ * ldsp_freqdem_create, a real prototype h of L taps and a decimation D:
+ *   d[c][t] = lm_atan2f(im, re) * ref,   (re, im) = conj(x[c][t-1]) * x[c][t]
+ *   y[c][n] = scale sum_{j<L} h[j] d[c][nD - j]            (d = 0 before t = 0)
+ * d[c][t] is computed operation for operation as ldsp_freqdem_demodulate
+ * computes it.  The column schedule is the Channelizer's: output n is emitted
+ * by the call that delivers sample nD of every row; with T samples per row seen
+ * before a call and skip = (-T) mod D, a call of K samples per row returns
+ * K > skip ? ceil((K - skip) / D) : 0 columns; calls of any K, 0 included, are
+ * allowed.  A row's bits depend neither on how the stream is cut into calls nor
+ * on the other rows, their number or order.
+ *   1 <= C <= 256, fixed at creation;  kf > 0;  1 <= D <= 64;  1 <= L <= 17 D;
+ *   1 <= m <= 8.
+ * ldsp_fmbank_create designs h = firdes_kaiser(2 D m + 1, fc, as, 0) (fc <= 0:
+ * 0.5 / D) and sets scale = 1 / sum(h); with D = 1 it designs nothing and the
+ * object is the discriminator alone: y = d with no filter arithmetic, every row
+ * ldsp_freqdem_demodulate's bits, L reported as 0, scale 1 and not settable.
+ * ldsp_fmbank_create_taps takes h as given with scale = 1 (D = 1 allowed: a
+ * full-rate filter).  C, D or kf out of range, L = 0, m = 0, as <= 0 and
+ * fc >= 0.5 are LDSP_EINVAL; L > 17 D and m > 8 are LDSP_EUNSUP.
+ * ldsp_fmbank_execute reads row c at x + c * ldx and writes float32 row c to
+ * y + c * ldy (both in samples, ldx >= K); it sets *ncols and, when
+ * ldy < *ncols, returns LDSP_ERANGE without consuming the input.  Argument
+ * errors are decided on the host before any device work.
+ * Not built: de-emphasis and squelch over rows, a per-row kf.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_fmbank_s *ldsp_fmbank_t;
+int ldsp_fmbank_create(unsigned int C, float kf, unsigned int D, unsigned int m, float fc, float as, ldsp_fmbank_t *q);
+int ldsp_fmbank_create_taps(unsigned int C, float kf, unsigned int D, const float *h, unsigned int L,
+                            ldsp_fmbank_t *q);
+int ldsp_fmbank_destroy(ldsp_fmbank_t q);
+int ldsp_fmbank_reset(ldsp_fmbank_t q);
+/* Any pointer may be NULL.  skip: input samples per row before the next call's first output. */
+int ldsp_fmbank_get_info(ldsp_fmbank_t q, unsigned int *C, unsigned int *D, unsigned int *L, unsigned int *skip);
+int ldsp_fmbank_get_taps(ldsp_fmbank_t q, float *h);             /* L floats */
+int ldsp_fmbank_get_scale(ldsp_fmbank_t q, float *s);
+int ldsp_fmbank_set_scale(ldsp_fmbank_t q, float s);             /* LDSP_EINVAL for the discriminator alone */
+int ldsp_fmbank_num_outputs(ldsp_fmbank_t q, size_t K, size_t *ncols);
+int ldsp_fmbank_execute(ldsp_fmbank_t q, const void *x, size_t ldx, size_t K, void *y, size_t ldy, size_t *ncols,
+                        int mem, void *stream);
+/* Test hook: output columns per workgroup of the (D, L) kernel (L = 0: the discriminator alone). */
+int ldsp_debug_fmbank_tile(unsigned int D, unsigned int L, size_t *frames);
+
+/* ------------------------------------------------------------------------
  * Spectrogram: a streaming Welch periodogram, one complex64 stream to rows of
  * power per bin and a running mean of them.  No reference counterpart
  * (liquid's spgramcf / spwaterfallcf are the same block: a zeroed window

@@ -1338,6 +1338,39 @@ struct ldsp_ddc_s : ldsp::DevObj {
     }
 };
 
+// FMBank (discriminator and decimating FIR over bank rows): the prototype (none:
+// the discriminator alone, D = 1), the host-side stream position (skip follows
+// from it), and on the device the taps in the kernel's layout (kernels.hpp),
+// per row the last L - 1 discriminator values and the last raw sample, both
+// ping-ponged.  The history holds discriminator values, so zeroed buffers are
+// the definition's "d = 0 before t = 0".
+struct ldsp_fmbank_s : ldsp::DevObj {
+    unsigned int C = 0, D = 1;
+    float ref = 0.0f;                      // (float)(1 / (2 pi kf))
+    std::vector<float> h;                  // empty: the discriminator alone
+    float scale = 1.0f;
+    uint64_t seen = 0;                     // input samples per row since create / reset
+    ldsp::DevBuf dtaps;
+    ldsp::PingPong dhist, prev;
+    size_t hist_bytes() const { return std::max<size_t>((size_t)C * (h.empty() ? 0 : h.size() - 1), 1) * 4; }
+    size_t skip() const { return (size_t)((D - seen % D) % D); }
+    size_t num_outputs(size_t n) const { return n > skip() ? (n - skip() + D - 1) / D : 0; }
+    void zero_state(int dev)
+    {
+        dhist.zero(hist_bytes(), dev);
+        prev.zero((size_t)C * 8, dev);
+    }
+    void bind(int dev)
+    {
+        // t[r][q] = h[L - 1 - (q D + r)], zero past the prototype's end
+        const size_t L = h.size(), QP = (L + D - 1) / D;
+        std::vector<float> t((size_t)D * QP, 0.0f);
+        for (size_t k = 0; k < L; k++) t[(k % D) * QP + k / D] = h[L - 1 - k];
+        ldsp::upload(dtaps, t, dev);
+        zero_state(dev);
+    }
+};
+
 // Spectrogram (streaming Welch periodogram): the window, the host-side counts
 // (samples since reset, transforms since clear; the schedule follows from
 // them), and on the device the padded window, the twiddle table, the last
@@ -3702,6 +3735,161 @@ int ldsp_debug_ddc_tile(unsigned int D, unsigned int L, size_t* frames)
         LDSP_REQUIRE(L >= 1, "ddc: at least one tap");
         if (L > (unsigned)k::kChanMaxP * D) throw Error(LDSP_EUNSUP, "ddc: more than 17 taps per output phase is not implemented");
         *frames = (size_t)k::ddc_frames((int)D, (int)L);
+    });
+}
+
+// ---------------------------------------------------------------- FMBank
+static ldsp_fmbank_s* fmbank_make(unsigned int C, float kf, unsigned int D, std::vector<float> h, float scale)
+{
+    std::unique_ptr<ldsp_fmbank_s> o(new ldsp_fmbank_s());
+    o->C = C;
+    o->D = D;
+    o->ref = (float)(1.0 / (2 * M_PI * (double)kf));   // as ldsp_freqdem_create
+    o->h = std::move(h);
+    o->scale = scale;
+    return o.release();
+}
+static void fmbank_check_shape(unsigned int C, float kf, unsigned int D)
+{
+    LDSP_REQUIRE(C >= 1 && C <= (unsigned)k::kFmbankMaxC,
+                 "fmbank: the row count must lie in 1 .. " + std::to_string(k::kFmbankMaxC));
+    LDSP_REQUIRE(kf > 0.0f, "fmbank: kf must be > 0");
+    LDSP_REQUIRE(D >= 1 && D <= (unsigned)k::kFmbankMaxD,
+                 "fmbank: the decimation must lie in 1 .. " + std::to_string(k::kFmbankMaxD));
+}
+int ldsp_fmbank_create(unsigned int C, float kf, unsigned int D, unsigned int m, float fc, float as, ldsp_fmbank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        fmbank_check_shape(C, kf, D);
+        LDSP_REQUIRE(m >= 1, "fmbank: filter semi-length must be at least 1");
+        LDSP_REQUIRE(as > 0.0f, "fmbank: stop-band attenuation must be > 0");
+        LDSP_REQUIRE(fc < 0.5f, "fmbank: cutoff must be below 0.5");
+        if (2 * (size_t)m + 1 > (size_t)k::kChanMaxP)
+            throw Error(LDSP_EUNSUP, "fmbank: semi-length above " + std::to_string((k::kChanMaxP - 1) / 2) +
+                                         " is not implemented");
+        if (D == 1) {                                  // nothing to decimate: the discriminator alone
+            *q = fmbank_make(C, kf, D, {}, 1.0f);
+            return;
+        }
+        std::vector<float> h = design::firdes_kaiser(2 * D * m + 1, fc > 0.0f ? fc : 0.5f / (float)D, as, 0.0f);
+        double sum = 0.0;
+        for (float v : h) sum += (double)v;
+        *q = fmbank_make(C, kf, D, std::move(h), (float)(1.0 / sum));
+    });
+}
+int ldsp_fmbank_create_taps(unsigned int C, float kf, unsigned int D, const float* h, unsigned int L, ldsp_fmbank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        fmbank_check_shape(C, kf, D);
+        LDSP_REQUIRE(L >= 1, "fmbank: at least one tap");
+        NONNULL(h);
+        if (L > (unsigned)k::kChanMaxP * D)
+            throw Error(LDSP_EUNSUP, "fmbank: more than " + std::to_string(k::kChanMaxP) + " taps per output phase (L > " +
+                                         std::to_string(k::kChanMaxP) + " D) is not implemented");
+        *q = fmbank_make(C, kf, D, std::vector<float>(h, h + L), 1.0f);
+    });
+}
+int ldsp_fmbank_destroy(ldsp_fmbank_t q) { return guard([&] { destroy(q); }); }
+int ldsp_fmbank_reset(ldsp_fmbank_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        q->seen = 0;
+        q->at_rest([&] { q->zero_state(q->device); });
+    });
+}
+int ldsp_fmbank_get_info(ldsp_fmbank_t q, unsigned int* C, unsigned int* D, unsigned int* L, unsigned int* skip)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (C) *C = q->C;
+        if (D) *D = q->D;
+        if (L) *L = (unsigned)q->h.size();
+        if (skip) *skip = (unsigned)q->skip();
+    });
+}
+int ldsp_fmbank_get_taps(ldsp_fmbank_t q, float* h)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(h);
+        std::copy(q->h.begin(), q->h.end(), h);
+    });
+}
+int ldsp_fmbank_get_scale(ldsp_fmbank_t q, float* s) { return guard([&] { NONNULL(q); NONNULL(s); *s = q->scale; }); }
+int ldsp_fmbank_set_scale(ldsp_fmbank_t q, float s)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(!q->h.empty(), "fmbank: the discriminator alone has no scale");
+        q->scale = s;
+    });
+}
+int ldsp_fmbank_num_outputs(ldsp_fmbank_t q, size_t K, size_t* ncols)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(ncols);
+        *ncols = q->num_outputs(K);
+    });
+}
+int ldsp_fmbank_execute(ldsp_fmbank_t q, const void* x, size_t ldx, size_t K, void* y, size_t ldy, size_t* ncols, int mem,
+                        void* stream)
+{
+    LDSP_RANGE("ldsp_fmbank_execute");
+    return guard([&] {
+        NONNULL(q);
+        const size_t N = q->num_outputs(K);
+        if (ncols) *ncols = N;
+        LDSP_REQUIRE(ldx >= K, "fmbank_execute: input row stride below the number of samples");
+        if (N > ldy) throw Error(LDSP_ERANGE, "fmbank_execute: output row stride below the number of output columns");
+        LDSP_REQUIRE(K == 0 || x, "fmbank_execute: NULL input");
+        LDSP_REQUIRE(N == 0 || y, "fmbank_execute: NULL output");
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
+        const size_t C = q->C;
+        // a host-memory call reads and writes dense [C][K] and [C][N] device images
+        // (rows of the caller's images are ldx and ldy samples apart)
+        const void* dx = q->stg.dev_in(e, x, K * 8, C, ldx * 8);
+        float* dy = (float*)q->stg.dev_out(e, y, C * N * 4);
+        if (K > 0) {
+            k::FmbankCall c;
+            c.x = dx;
+            c.dhist = (const float*)q->dhist.in();
+            c.dhist_out = (float*)q->dhist.out();
+            c.prev = q->prev.in();
+            c.prev_out = q->prev.out();
+            c.n = K;
+            c.ldx = e.host ? K : ldx;
+            c.skip = q->skip();
+            c.ncols = N;
+            c.ldy = e.host ? N : ldy;
+            c.C = (int)C;
+            c.L = (int)q->h.size();
+            c.taps = q->dtaps.as<float>();
+            c.ref = q->ref;
+            c.scale = q->scale;
+            c.y = dy;
+            k::fmbank((int)q->D, c, e.stream);
+            q->dhist.flip();
+            q->prev.flip();
+            q->seen += K;
+        }
+        call.end();
+        q->stg.finish(e, y, N * 4, C, ldy * 4);
+    });
+}
+int ldsp_debug_fmbank_tile(unsigned int D, unsigned int L, size_t* frames)
+{
+    return guard([&] {
+        NONNULL(frames);
+        LDSP_REQUIRE(D >= 1 && D <= (unsigned)k::kFmbankMaxD,
+                     "fmbank: the decimation must lie in 1 .. " + std::to_string(k::kFmbankMaxD));
+        if (L > (unsigned)k::kChanMaxP * D)
+            throw Error(LDSP_EUNSUP, "fmbank: more than 17 taps per output phase is not implemented");
+        *frames = L == 0 ? 256 : (size_t)k::fmbank_frames((int)D, (int)L);
     });
 }
 

@@ -15,6 +15,7 @@
 #include "kernels.hpp"
 #include "ldsp_common.hpp"
 #include "ldsp_math.hpp"
+#include "freqdem.hpp"
 
 namespace ldsp {
 namespace k {
@@ -52,11 +53,7 @@ __global__ void __launch_bounds__(256) k_freqdem(const float2* __restrict__ x, c
     for (long i = i0; i < n; i += stride) {
         const float2 rp = i > 0 ? x[i - 1] : prev[0];
         const float2 r = x[i];
-        // conjf(r') * r with the C99 float complex product: (a + j b')(c + j d), b' = -b
-        const float a = rp.x, bq = -rp.y;
-        const float re = a * r.x - bq * r.y;
-        const float im = a * r.y + bq * r.x;
-        y[i] = lm_atan2f(im, re) * ref;
+        y[i] = freqdem_disc(rp, r, ref);
     }
     if (i0 == 0) prev_out[0] = n > 0 ? x[n - 1] : prev[0];
 }

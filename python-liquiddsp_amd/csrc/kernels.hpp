@@ -431,6 +431,32 @@ struct DdcCall {
     void* y;
 };
 void ddc(int D, const DdcCall& c, hipStream_t s);
+// k_fmbank.hip: FM discriminator and decimating real FIR over bank rows (FMBank).
+// C <= kFmbankMaxC rows, decimation 1 <= D <= kFmbankMaxD, a real prototype of
+// L <= kChanMaxP D taps; L = 0 (D = 1 only) is the discriminator alone.
+// x: row c is n complex64 samples at x + c * ldx.  dhist / dhist_out: per row the
+// L - 1 discriminator values before the call's first / before the next call's
+// first, [C][L - 1]; prev / prev_out: per row the raw sample before x[c][0] /
+// the call's last; distinct buffers.  The call's columns are at sample
+// skip + m D, m < ncols, as k_chan's.  taps: the host's table [D][ceil(L / D)],
+// t[r][q] = h[L - 1 - (q D + r)] (zero where q D + r >= L).  y[c * ldy + m]
+// receives row c.  n = 0 launches nothing.
+constexpr int kFmbankMaxC = 256;
+constexpr int kFmbankMaxD = 64;
+int fmbank_frames(int D, int L);                            // output columns per workgroup
+struct FmbankCall {
+    const void* x;
+    const float* dhist;
+    float* dhist_out;
+    const void* prev;
+    void* prev_out;
+    size_t n, ldx, skip, ncols, ldy;
+    int C, L;
+    const float* taps;
+    float ref, scale;
+    float* y;
+};
+void fmbank(int D, const FmbankCall& c, hipStream_t s);
 // k_synth.hip: polyphase synthesis filter bank (Synthesizer), k_chan's
 // counterpart.  M rows (a power of two, 4 .. 256), interpolation D = M or M / 2,
 // Q = ceil(L / D) <= synth_qmax(M, D) taps per output residue.  y: row k at

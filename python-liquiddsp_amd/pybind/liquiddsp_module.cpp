@@ -1133,6 +1133,131 @@ struct Downconverter {
     }
 };
 
+// ------------------------------------------------------------------ FMBank (liquid: freqdem + firdecim_rrrf per row)
+// Discriminator and decimating FIR over bank rows (ldsp.h): complex64[nchan, K]
+// -> float32[nchan, ncols].  A device tensor whose columns are one sample apart
+// and whose rows do not overlap (a block of rows or a range of columns of a
+// Channelizer or Downconverter output) is read in place.
+struct FMBank {
+    ldsp_fmbank_t q = nullptr;
+    unsigned C = 0, D = 0, L = 0;
+    float kf;
+    FMBank(int nchan, float kf_, int decim, int m, const py::object& fc, float as, const py::object& taps) : kf(kf_)
+    {
+        if (nchan < 0) throw py::value_error("FMBank: nchan must lie in 1 .. 256");
+        if (decim < 0) throw py::value_error("FMBank: decim must lie in 1 .. 64");
+        if (!taps.is_none()) {
+            std::vector<float> h = to_fvec(taps);
+            check(ldsp_fmbank_create_taps((unsigned)nchan, kf, (unsigned)decim, h.data(), (unsigned)h.size(), &q));
+        } else {
+            if (m < 0) throw py::value_error("FMBank: m must be >= 1");
+            float c = 0.0f;                                   // the C ABI's default: 0.5 / decim
+            if (!fc.is_none()) {
+                c = fc.cast<float>();
+                if (!(c > 0.0f && c < 0.5f)) throw py::value_error("FMBank: Fc must lie in (0, 0.5)");
+            }
+            check(ldsp_fmbank_create((unsigned)nchan, kf, (unsigned)decim, (unsigned)m, c, as, &q));
+        }
+        check(ldsp_fmbank_get_info(q, &C, &D, &L, nullptr));
+    }
+    FMBank(const FMBank&) = delete;
+    ~FMBank()
+    {
+        if (q) ldsp_fmbank_destroy(q);
+    }
+    void reset() { check(ldsp_fmbank_reset(q)); }
+    py::array_t<float> taps()
+    {
+        py::array_t<float> h(L);
+        if (L) check(ldsp_fmbank_get_taps(q, h.mutable_data()));
+        return h;
+    }
+    float get_scale()
+    {
+        float s;
+        check(ldsp_fmbank_get_scale(q, &s));
+        return s;
+    }
+    void set_scale(float s) { check(ldsp_fmbank_set_scale(q, s)); }
+    unsigned skip()
+    {
+        unsigned s;
+        check(ldsp_fmbank_get_info(q, nullptr, nullptr, nullptr, &s));
+        return s;
+    }
+    size_t tile()
+    {
+        size_t f = 0;
+        check(ldsp_debug_fmbank_tile(D, L, &f));
+        return f;
+    }
+    size_t num_outputs(size_t K)
+    {
+        size_t c = 0;
+        check(ldsp_fmbank_num_outputs(q, K, &c));
+        return c;
+    }
+    void check_rows(py::ssize_t ndim, py::ssize_t rows) const
+    {
+        if (ndim != 2) throw py::value_error("FMBank: the input must be 2-D, [nchan, K] (1-D when nchan is 1)");
+        if (rows != (py::ssize_t)C)
+            throw py::value_error("FMBank: the input has " + std::to_string(rows) + " rows, nchan is " +
+                                  std::to_string(C));
+    }
+    py::object call(const py::handle& x)
+    {
+        size_t nw = 0;
+        if (is_device_tensor(x)) {
+            py::object& torch = torch_mod();
+            py::object t = py::reinterpret_borrow<py::object>(x);
+            if (C == 1 && t.attr("dim")().cast<int>() == 1) t = t.attr("unsqueeze")(0);
+            check_rows(t.attr("dim")().cast<py::ssize_t>(), t.attr("dim")().cast<int>() == 2
+                                                                ? t.attr("size")(0).cast<py::ssize_t>()
+                                                                : 0);
+            if (!py::object(t.attr("dtype")).equal(torch.attr("complex64"))) t = t.attr("to")(torch.attr("complex64"));
+            const size_t K = t.attr("size")(1).cast<size_t>();
+            // read in place: columns one sample apart, rows that do not overlap
+            if (K > 1 && t.attr("stride")(1).cast<long>() != 1)
+                throw py::value_error("FMBank: the input's columns must be one sample apart (stride(1) == 1)");
+            if (C > 1 && t.attr("stride")(0).cast<long>() < (long)K)
+                throw py::value_error("FMBank: the input's row stride must be at least its number of columns");
+            const size_t ldx = C > 1 ? t.attr("stride")(0).cast<size_t>() : K;
+            py::object device = t.attr("device");
+            const int tdev = device.attr("index").cast<int>();
+            const int cur = torch.attr("cuda").attr("current_device")().cast<int>();
+            if (tdev != cur)
+                throw py::value_error("input tensor is on cuda:" + std::to_string(tdev) +
+                                      " but the current device is cuda:" + std::to_string(cur) +
+                                      " (call under torch.cuda.device(" + std::to_string(tdev) + "))");
+            void* stream = reinterpret_cast<void*>(
+                torch.attr("cuda").attr("current_stream")(device).attr("cuda_stream").cast<uintptr_t>());
+            const size_t N = num_outputs(K);
+            py::dict kw;
+            kw["dtype"] = torch.attr("float32");
+            kw["device"] = device;
+            py::object out = torch.attr("empty")(py::make_tuple(C, N), **kw);
+            check(ldsp_fmbank_execute(q, tptr(t), ldx, K, tptr(out), N, &nw, LDSP_MEM_DEVICE, stream));
+            return out;
+        }
+        carr a = carr::ensure(x);
+        if (!a) throw py::error_already_set();
+        if (C == 1 && a.ndim() == 1) a = a.reshape({(py::ssize_t)1, a.shape(0)});
+        check_rows(a.ndim(), a.ndim() == 2 ? a.shape(0) : 0);
+        const size_t K = (size_t)a.shape(1);
+        const size_t N = num_outputs(K);
+        py::array_t<float> out({(py::ssize_t)C, (py::ssize_t)N});
+        void* yp = out.mutable_data();
+        const void* xp = a.data();
+        int rc;
+        {
+            py::gil_scoped_release rel;
+            rc = ldsp_fmbank_execute(q, xp, K, K, yp, N, &nw, LDSP_MEM_HOST, nullptr);
+        }
+        check(rc);
+        return out;
+    }
+};
+
 // ------------------------------------------------------------------ Synthesizer (no reference counterpart)
 // Polyphase synthesis bank (ldsp.h): complex64[nchan, K] -> complex64[K * interp],
 // row k mixed up to k / nchan.  A device tensor whose columns are contiguous (a
@@ -2002,6 +2127,23 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def_property_readonly("skip", &Downconverter::skip, "input samples before the next call's first output")
         .def_property_readonly("tile", &Downconverter::tile, "output columns per workgroup of the kernel")
         .def("__call__", &Downconverter::call, "complex64[N] -> complex64[ntuners, ncols]");
+
+    // ---- FMBank (beyond the reference: discriminator and decimating FIR over bank rows)
+    py::class_<FMBank>(m, "FMBank")
+        .def(py::init<int, float, int, int, py::object, float, py::object>(), py::arg("nchan"), py::arg("kf"),
+             py::arg("decim") = 1, py::arg("m") = 6, py::arg("Fc") = py::none(), py::arg("As") = 60.0f,
+             py::arg("taps") = py::none())
+        .def("reset", &FMBank::reset)
+        .def("num_outputs", &FMBank::num_outputs, py::arg("K"),
+             "columns the next call returns for K input samples per row")
+        .def_property_readonly("nchan", [](FMBank& c) { return c.C; })
+        .def_property_readonly("kf", [](FMBank& c) { return c.kf; })
+        .def_property_readonly("decim", [](FMBank& c) { return c.D; })
+        .def_property_readonly("taps", &FMBank::taps, "the prototype; empty for the discriminator alone")
+        .def_property("scale", &FMBank::get_scale, &FMBank::set_scale)
+        .def_property_readonly("skip", &FMBank::skip, "input samples per row before the next call's first output")
+        .def_property_readonly("tile", &FMBank::tile, "output columns per workgroup of the kernel")
+        .def("__call__", &FMBank::call, "complex64[nchan, K] -> float32[nchan, ncols]");
 
     // ---- Synthesizer (beyond the reference: polyphase synthesis filter bank)
     py::class_<Synthesizer>(m, "Synthesizer")
