@@ -682,7 +682,8 @@ int ldsp_debug_ddc_seek(ldsp_ddc_t q, uint64_t T);
  * y + c * ldy (both in samples, ldx >= K); it sets *ncols and, when
  * ldy < *ncols, returns LDSP_ERANGE without consuming the input.  Argument
  * errors are decided on the host before any device work.
- * Not built: de-emphasis and squelch over rows, a per-row kf.
+ * De-emphasis and rate conversion over the rows it writes: AudioBank, below.
+ * Not built: squelch over rows, a per-row kf.
  * ---------------------------------------------------------------------- */
 typedef struct ldsp_fmbank_s *ldsp_fmbank_t;
 int ldsp_fmbank_create(unsigned int C, float kf, unsigned int D, unsigned int m, float fc, float as, ldsp_fmbank_t *q);
@@ -700,6 +701,64 @@ int ldsp_fmbank_execute(ldsp_fmbank_t q, const void *x, size_t ldx, size_t K, vo
                         int mem, void *stream);
 /* Test hook: output columns per workgroup of the (D, L) kernel (L = 0: the discriminator alone). */
 int ldsp_debug_fmbank_tile(unsigned int D, unsigned int L, size_t *frames);
+
+/* ------------------------------------------------------------------------
+ * AudioBank: for every row of a float32 [C][K] block (an FMBank output, read in
+ * place), an optional one-pole de-emphasis at the input rate followed by
+ * liquid's arbitrary-rate polyphase resampler and an optional 16-bit PCM store,
+ * in one pass; the de-emphasised signal stays on the chip.  liquid's
+ * counterpart is iirfilt_rrrf (one pole) + resamp_rrrf per row (the reference's
+ * FM receiver, src/demod.hpp:19-31, 75-82).  For row c of the concatenated
+ * input u[c][t] (t counted from 0 since creation or reset, u = 0 before that):
+ *   a  = (float) exp(-1 / (tau * (double)sample_rate)),   b0 = (float)(1 - (double)a)
+ *   e[c][t] = b0 sum_{j>=0} a^j u[c][t-j]         (de-emphasis off: e = u, no arithmetic)
+ *   y[c][k] = sum_{n<2m} h_{b_k}[n] e[c][j_k - n]
+ *   z = y * scale;   float32 out = z;
+ *   pcm16 out = (int16) clamp(rintf(z * 32767.0f), -32768, 32767)
+ * The prototype, the rounding of npfb to a power of two, step = round(2^24 /
+ * rate), the fixed-point phase schedule (j_k, b_k) and the dot product's order
+ * are ldsp_resamp's (kind 0, resamp_rrrf): without de-emphasis and at scale 1
+ * every row carries ldsp_resamp_execute's bits, and *nout is its count call by
+ * call, the same for every row.  At tau = 75e-6 the coefficients a and b0 are
+ * DeemphasisFilter's.  With de-emphasis every row is within 1e-6 of the float64
+ * evaluation of the lines above (max-norm, relative to the row's maximum); the
+ * recursion's state is kept in float64 (liquid's float32 state misses that gate
+ * on a constant row).  A row's bits depend neither on how the stream is cut into
+ * calls, nor on the other rows, their number or order, nor on the row strides.
+ *   1 <= C <= 256, fixed at creation;  1/32 <= rate <= 4;  1 <= m <= 32;
+ *   npfb (rounded) * 2m <= 8192;  tau * sample_rate <= 32 input samples.
+ * ldsp_audiobank_create: sample_rate <= 0 means no de-emphasis (tau is then not
+ * looked at).  C out of range, rate <= 0, m = 0, fc outside (0, 0.5), as <= 0,
+ * npfb = 0, and tau <= 0 with de-emphasis are LDSP_EINVAL; a rate outside
+ * [1/32, 4], m > 32, more than 8192 branch taps and tau * sample_rate > 32 are
+ * LDSP_EUNSUP.
+ * ldsp_audiobank_execute reads row c at x + c * ldx and writes row c (float32,
+ * or int16 with pcm16) to y + c * ldy, both in samples (ldx >= K); it sets *nout
+ * and, when ldy < *nout, returns LDSP_ERANGE without consuming the input.
+ * K = 0 and calls too short for an output are allowed; they carry state only.
+ * Argument errors are decided on the host before any device work.
+ * Not built: a mid-stream rate setter, complex rows, per-row rates or time
+ * constants, de-emphasis after the resampler.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_audiobank_s *ldsp_audiobank_t;
+int ldsp_audiobank_create(unsigned int C, float rate, unsigned int m, float fc, float as, unsigned int npfb,
+                          float sample_rate, double tau, int pcm16, ldsp_audiobank_t *q);
+int ldsp_audiobank_destroy(ldsp_audiobank_t q);
+int ldsp_audiobank_reset(ldsp_audiobank_t q);
+/* Any pointer may be NULL.  npfb: after the rounding; phase: the schedule's, as ldsp_resamp_get_info's. */
+int ldsp_audiobank_get_info(ldsp_audiobank_t q, unsigned int *C, unsigned int *npfb, uint32_t *step, uint32_t *phase,
+                            unsigned int *sub_len);
+/* As ldsp_resamp_get_taps: the prototype of 2 m npfb + 1 taps; h may be NULL to ask for *n. */
+int ldsp_audiobank_get_taps(ldsp_audiobank_t q, float *h, unsigned int cap, unsigned int *n);
+/* Any pointer may be NULL.  Without de-emphasis: b0 = 1, a = 0, sample_rate = 0, tau = 0. */
+int ldsp_audiobank_get_coefs(ldsp_audiobank_t q, float *b0, float *a, float *sample_rate, double *tau);
+int ldsp_audiobank_get_scale(ldsp_audiobank_t q, float *s);
+int ldsp_audiobank_set_scale(ldsp_audiobank_t q, float s);
+int ldsp_audiobank_num_outputs(ldsp_audiobank_t q, size_t K, size_t *nout);
+int ldsp_audiobank_execute(ldsp_audiobank_t q, const void *x, size_t ldx, size_t K, void *y, size_t ldy, size_t *nout,
+                           int mem, void *stream);
+/* Test hook: outputs per workgroup of the kernel this object launches. */
+int ldsp_debug_audiobank_tile(ldsp_audiobank_t q, size_t *outputs);
 
 /* ------------------------------------------------------------------------
  * Spectrogram: a streaming Welch periodogram, one complex64 stream to rows of

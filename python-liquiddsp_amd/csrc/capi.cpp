@@ -1371,6 +1371,44 @@ struct ldsp_fmbank_s : ldsp::DevObj {
     }
 };
 
+// AudioBank (de-emphasis and polyphase resampler over bank rows): the resampler's
+// design and its host-side phase (as ResampObj's), the de-emphasis coefficients
+// and warm-up (J = 0: none), the samples per row since reset (the de-emphasis
+// grid is absolute), and on the device the branch table in the kernel's layout
+// and per row the last H raw input samples, ping-ponged.
+struct ldsp_audiobank_s : ldsp::DevObj {
+    unsigned int C = 0, m = 0, npfb = 0, sub_len = 0;
+    int bits_index = 0;
+    float rate = 1.0f;
+    uint32_t step = 0;
+    uint64_t phase = 0, seen = 0;
+    std::vector<float> hproto, sub;        // sub: [npfb][sub_len] reversed
+    float sample_rate = 0.0f;              // <= 0: no de-emphasis
+    double tau = 0.0;
+    float a = 0.0f, b0 = 1.0f;
+    int J = 0, H = 0;
+    bool pcm16 = false;
+    float scale = 1.0f;
+    ldsp::DevBuf dsub;
+    ldsp::PingPong hist;
+    size_t hist_bytes() const { return (size_t)C * H * 4; }
+    size_t osz() const { return pcm16 ? 2 : 4; }
+    size_t num_outputs(size_t n) const     // ResampObj::num_outputs
+    {
+        if (n == 0) return 0;
+        const long long num = (long long)(n - 1) * (1LL << 24) + 0xffffffLL - (long long)phase;
+        return num < 0 ? 0 : (size_t)(num / step) + 1;
+    }
+    int tile() const { return ldsp::k::audiobank_tile(step, (int)sub_len, (int)npfb, J); }
+    void bind(int dev)
+    {
+        std::vector<float> t((size_t)npfb * (sub_len + 1), 0.0f);   // rows padded to an odd length
+        for (size_t b = 0; b < npfb; b++) std::copy_n(&sub[b * sub_len], sub_len, &t[b * (sub_len + 1)]);
+        ldsp::upload(dsub, t, dev);
+        hist.zero(hist_bytes(), dev);
+    }
+};
+
 // Spectrogram (streaming Welch periodogram): the window, the host-side counts
 // (samples since reset, transforms since clear; the schedule follows from
 // them), and on the device the padded window, the twiddle table, the last
@@ -1757,6 +1795,38 @@ int ldsp_firfilt_execute(ldsp_firfilt_t q, const void* x, size_t n, void* y, int
 }
 
 // ---------------------------------------------------------------- resampler
+// resamp_*_create's filter (ldsp_resamp_create, ldsp_audiobank_create): npfb rounded
+// up to a power of two, the Kaiser prototype of 2 m npfb + 1 taps scaled to a DC
+// gain of npfb, and its branches reversed, [npfb][sub_len] with c floats per tap
+// (c = 2: complex taps, imaginary parts 0)
+struct ResampDesign {
+    unsigned int npfb = 0, sub_len = 0;
+    int bits_index = 0;
+    std::vector<float> hproto, sub;
+};
+static ResampDesign resamp_design(unsigned int m, float fc, float as, unsigned int npfb, unsigned int c)
+{
+    ResampDesign d;
+    unsigned int bits = 0;
+    for (unsigned int v = npfb - 1; v; v >>= 1) bits++;   // liquid_nextpow2
+    LDSP_REQUIRE(bits <= 16, "resamp: too many filters");
+    d.npfb = 1u << bits;
+    d.bits_index = 24 - (int)bits;
+    const unsigned int n = 2 * m * d.npfb + 1;
+    std::vector<float> hf = design::firdes_kaiser(n, fc / ((float)d.npfb), as, 0.0f);
+    float gain = 0.0f;
+    for (float v : hf) gain += v;
+    gain = (float)d.npfb / gain;
+    d.hproto.resize(n);
+    for (unsigned int i = 0; i < n; i++) d.hproto[i] = hf[i] * gain;
+    d.sub_len = (n - 1) / d.npfb;
+    d.sub.assign((size_t)d.npfb * d.sub_len * c, 0.0f);
+    for (unsigned int b = 0; b < d.npfb; b++)
+        for (unsigned int k = 0; k < d.sub_len; k++)
+            d.sub[((size_t)b * d.sub_len + (d.sub_len - k - 1)) * c] = d.hproto[b + k * d.npfb];
+    return d;
+}
+
 int ldsp_resamp_create(float rate, unsigned int m, float fc, float as, unsigned int npfb, int cplx, ldsp_resamp_t* q)
 {
     return guard([&] {
@@ -1773,24 +1843,12 @@ int ldsp_resamp_create(float rate, unsigned int m, float fc, float as, unsigned 
         o->m = m;
         o->fc = fc;
         o->as = as;
-        unsigned int bits = 0;
-        for (unsigned int v = npfb - 1; v; v >>= 1) bits++;   // liquid_nextpow2
-        LDSP_REQUIRE(bits <= 16, "resamp: too many filters");
-        o->npfb = 1u << bits;
-        o->bits_index = 24 - (int)bits;
-        const unsigned int n = 2 * m * o->npfb + 1;
-        std::vector<float> hf = design::firdes_kaiser(n, fc / ((float)o->npfb), as, 0.0f);
-        float gain = 0.0f;
-        for (float v : hf) gain += v;
-        gain = (float)o->npfb / gain;
-        o->hproto.resize(n);
-        for (unsigned int i = 0; i < n; i++) o->hproto[i] = hf[i] * gain;
-        o->sub_len = (n - 1) / o->npfb;
-        const unsigned c = (o->cplx && !o->real_taps) ? 2 : 1;
-        o->sub.assign((size_t)o->npfb * o->sub_len * c, 0.0f);
-        for (unsigned int b = 0; b < o->npfb; b++)
-            for (unsigned int k = 0; k < o->sub_len; k++)
-                o->sub[((size_t)b * o->sub_len + (o->sub_len - k - 1)) * c] = o->hproto[b + k * o->npfb];
+        ResampDesign d = resamp_design(m, fc, as, npfb, (o->cplx && !o->real_taps) ? 2 : 1);
+        o->npfb = d.npfb;
+        o->bits_index = d.bits_index;
+        o->sub_len = d.sub_len;
+        o->hproto = std::move(d.hproto);
+        o->sub = std::move(d.sub);
         *q = o.release();
     });
 }
@@ -3890,6 +3948,173 @@ int ldsp_debug_fmbank_tile(unsigned int D, unsigned int L, size_t* frames)
         if (L > (unsigned)k::kChanMaxP * D)
             throw Error(LDSP_EUNSUP, "fmbank: more than 17 taps per output phase is not implemented");
         *frames = L == 0 ? 256 : (size_t)k::fmbank_frames((int)D, (int)L);
+    });
+}
+
+// ---------------------------------------------------------------- AudioBank
+int ldsp_audiobank_create(unsigned int C, float rate, unsigned int m, float fc, float as, unsigned int npfb,
+                          float sample_rate, double tau, int pcm16, ldsp_audiobank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        const bool de = sample_rate > 0.0f;
+        LDSP_REQUIRE(C >= 1 && C <= (unsigned)k::kAudiobankMaxC,
+                     "audiobank: the row count must lie in 1 .. " + std::to_string(k::kAudiobankMaxC));
+        LDSP_REQUIRE(rate > 0.0f, "audiobank: resampling rate must be greater than zero");
+        LDSP_REQUIRE(m > 0, "audiobank: filter semi-length must be greater than zero");
+        LDSP_REQUIRE(fc > 0.0f && fc < 0.5f, "audiobank: filter cutoff must be in (0, 0.5)");
+        LDSP_REQUIRE(as > 0.0f, "audiobank: filter stop-band suppression must be greater than zero");
+        LDSP_REQUIRE(npfb > 0, "audiobank: number of filters must be greater than zero");
+        LDSP_REQUIRE(!de || tau > 0.0, "audiobank: the de-emphasis time constant must be greater than zero");
+        if (!(rate >= 1.0f / 32 && rate <= 4.0f))
+            throw Error(LDSP_EUNSUP, "audiobank: a rate outside [1/32, 4] is not implemented");
+        if (m > (unsigned)k::kAudiobankMaxM)
+            throw Error(LDSP_EUNSUP, "audiobank: semi-length above " + std::to_string(k::kAudiobankMaxM) +
+                                         " is not implemented");
+        uint64_t np2 = 1;
+        while (np2 < npfb) np2 <<= 1;                  // liquid_nextpow2
+        if (np2 * 2 * m > (uint64_t)k::kAudiobankMaxTaps)
+            throw Error(LDSP_EUNSUP, "audiobank: more than " + std::to_string(k::kAudiobankMaxTaps) +
+                                         " branch taps (nfilter * 2 len) is not implemented");
+        if (de && tau * (double)sample_rate > 32.0)
+            throw Error(LDSP_EUNSUP, "audiobank: a time constant above 32 input samples is not implemented");
+        std::unique_ptr<ldsp_audiobank_s> o(new ldsp_audiobank_s());
+        o->C = C;
+        o->m = m;
+        o->rate = rate;
+        o->step = (uint32_t)round((double)((float)(1 << 24) / rate));   // ResampObj::set_rate
+        ResampDesign d = resamp_design(m, fc, as, npfb, 1);
+        o->npfb = d.npfb;
+        o->bits_index = d.bits_index;
+        o->sub_len = d.sub_len;
+        o->hproto = std::move(d.hproto);
+        o->sub = std::move(d.sub);
+        o->pcm16 = pcm16 != 0;
+        if (de) {
+            // DeemphasisFilter's coefficients (reference src/iirfilter.hpp:366-372) at any tau
+            o->sample_rate = sample_rate;
+            o->tau = tau;
+            o->a = (float)exp(-1.0 / (tau * (double)sample_rate));
+            o->b0 = (float)(1.0 - (double)o->a);
+            // the warm-up: the smallest J with a^J <= 2^-30
+            int J = 1;
+            if (o->a > 0.0f) {
+                J = std::max(1, (int)ceil(30.0 * M_LN2 / -log((double)o->a)));
+                while (pow((double)o->a, J) > ldexp(1.0, -30)) J++;
+            }
+            o->J = k::audiobank_warmup(J);
+            LDSP_REQUIRE(o->J <= k::kAudiobankMaxJ, "audiobank: de-emphasis warm-up out of range");
+        }
+        o->H = k::audiobank_hist((int)o->sub_len, o->J);
+        *q = o.release();
+    });
+}
+int ldsp_audiobank_destroy(ldsp_audiobank_t q) { return guard([&] { destroy(q); }); }
+int ldsp_audiobank_reset(ldsp_audiobank_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        q->phase = 0;
+        q->seen = 0;
+        q->at_rest([&] { q->hist.zero(q->hist_bytes(), q->device); });
+    });
+}
+int ldsp_audiobank_get_info(ldsp_audiobank_t q, unsigned int* C, unsigned int* npfb, uint32_t* step, uint32_t* phase,
+                            unsigned int* sub_len)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (C) *C = q->C;
+        if (npfb) *npfb = q->npfb;
+        if (step) *step = q->step;
+        if (phase) *phase = (uint32_t)q->phase;
+        if (sub_len) *sub_len = q->sub_len;
+    });
+}
+int ldsp_audiobank_get_taps(ldsp_audiobank_t q, float* h, unsigned int cap, unsigned int* n)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (n) *n = (unsigned)q->hproto.size();
+        if (h) {
+            LDSP_REQUIRE(cap >= q->hproto.size(), "audiobank_get_taps: capacity too small");
+            std::copy(q->hproto.begin(), q->hproto.end(), h);
+        }
+    });
+}
+int ldsp_audiobank_get_coefs(ldsp_audiobank_t q, float* b0, float* a, float* sample_rate, double* tau)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (b0) *b0 = q->b0;
+        if (a) *a = q->a;
+        if (sample_rate) *sample_rate = q->sample_rate;
+        if (tau) *tau = q->tau;
+    });
+}
+int ldsp_audiobank_get_scale(ldsp_audiobank_t q, float* s) { return guard([&] { NONNULL(q); NONNULL(s); *s = q->scale; }); }
+int ldsp_audiobank_set_scale(ldsp_audiobank_t q, float s) { return guard([&] { NONNULL(q); q->scale = s; }); }
+int ldsp_audiobank_num_outputs(ldsp_audiobank_t q, size_t K, size_t* nout)
+{
+    return guard([&] { NONNULL(q); NONNULL(nout); *nout = q->num_outputs(K); });
+}
+int ldsp_audiobank_execute(ldsp_audiobank_t q, const void* x, size_t ldx, size_t K, void* y, size_t ldy, size_t* nout,
+                           int mem, void* stream)
+{
+    LDSP_RANGE("ldsp_audiobank_execute");
+    return guard([&] {
+        NONNULL(q);
+        const size_t N = q->num_outputs(K);
+        if (nout) *nout = N;
+        LDSP_REQUIRE(ldx >= K, "audiobank_execute: input row stride below the number of samples");
+        if (N > ldy) throw Error(LDSP_ERANGE, "audiobank_execute: output row stride below the number of outputs");
+        LDSP_REQUIRE(K == 0 || x, "audiobank_execute: NULL input");
+        LDSP_REQUIRE(N == 0 || y, "audiobank_execute: NULL output");
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
+        const size_t C = q->C, osz = q->osz();
+        // a host-memory call reads and writes dense [C][K] and [C][N] device images
+        const void* dx = q->stg.dev_in(e, x, K * 4, C, ldx * 4);
+        void* dy = q->stg.dev_out(e, y, C * N * osz);
+        if (K > 0) {
+            k::AudiobankCall c;
+            c.x = (const float*)dx;
+            c.hist = (const float*)q->hist.in();
+            c.hist_out = (float*)q->hist.out();
+            c.n = K;
+            c.ldx = e.host ? K : ldx;
+            c.K = N;
+            c.ldy = e.host ? N : ldy;
+            c.P0 = q->phase;
+            c.seen = q->seen;
+            c.step = q->step;
+            c.bits_index = q->bits_index;
+            c.sub_len = (int)q->sub_len;
+            c.npfb = (int)q->npfb;
+            c.C = (int)C;
+            c.J = q->J;
+            c.H = q->H;
+            c.a = (double)q->a;
+            c.b0 = (double)q->b0;
+            c.sub = q->dsub.as<float>();
+            c.scale = q->scale;
+            c.pcm16 = q->pcm16 ? 1 : 0;
+            c.y = dy;
+            k::audiobank(c, e.stream);
+            q->hist.flip();
+            q->phase = (uint64_t)((long long)q->phase + (long long)N * q->step - (long long)K * (1LL << 24));
+            q->seen += K;
+        }
+        call.end();
+        q->stg.finish(e, y, N * osz, C, ldy * osz);
+    });
+}
+int ldsp_debug_audiobank_tile(ldsp_audiobank_t q, size_t* outputs)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(outputs);
+        *outputs = (size_t)q->tile();
     });
 }
 

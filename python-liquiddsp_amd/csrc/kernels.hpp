@@ -457,6 +457,41 @@ struct FmbankCall {
     float* y;
 };
 void fmbank(int D, const FmbankCall& c, hipStream_t s);
+// k_audiobank.hip: de-emphasis and polyphase resampler over bank rows (AudioBank).
+// C <= kAudiobankMaxC rows of float32, row c's n samples at x + c * ldx; the
+// resampler's schedule (P0, step, bits_index) and branches (sub_len = 2m <=
+// 2 kAudiobankMaxM taps each, npfb sub_len <= kAudiobankMaxTaps) are
+// ResampPlan's.  sub: the branch taps reversed as the resampler kernels take
+// them, rows padded to sub_len + 1 floats, [npfb][sub_len + 1].  J > 0: de-emphasis
+// e = b0 sum a^j u with a warm-up of J <= kAudiobankMaxJ samples (a^J <= 2^-30, J
+// from audiobank_warmup: whole blocks of the kernel's de-emphasis grid); J = 0: none.  seen: the samples per row before the call (the de-emphasis grid is
+// absolute).  hist / hist_out: per row the H = audiobank_hist(sub_len, J) raw
+// samples before x[c][0] / before the next call's first, [C][H], distinct buffers.
+// y[c * ldy + k], k < K, receives row c: float32, or int16 with pcm16 (ldy in
+// samples of the output type).  n = 0 launches nothing.
+constexpr int kAudiobankMaxC = 256;
+constexpr int kAudiobankMaxM = 32;
+constexpr int kAudiobankMaxTaps = 8192;
+constexpr int kAudiobankMaxJ = 693;                         // a^J <= 2^-30 at tau sample_rate = 32 takes 666
+int audiobank_warmup(int J);                                // J rounded up to whole blocks
+int audiobank_hist(int sub_len, int J);
+int audiobank_tile(uint32_t step, int sub_len, int npfb, int J);   // outputs per workgroup
+struct AudiobankCall {
+    const float* x;
+    const float* hist;
+    float* hist_out;
+    size_t n, ldx, K, ldy;
+    uint64_t P0, seen;
+    uint32_t step;
+    int bits_index, sub_len, npfb;
+    int C, J, H;
+    double a, b0;
+    const float* sub;
+    float scale;
+    int pcm16;
+    void* y;
+};
+void audiobank(const AudiobankCall& c, hipStream_t s);
 // k_synth.hip: polyphase synthesis filter bank (Synthesizer), k_chan's
 // counterpart.  M rows (a power of two, 4 .. 256), interpolation D = M or M / 2,
 // Q = ceil(L / D) <= synth_qmax(M, D) taps per output residue.  y: row k at

@@ -1258,6 +1258,159 @@ struct FMBank {
     }
 };
 
+// ------------------------------------------------------------------ AudioBank (liquid: iirfilt_rrrf + resamp_rrrf per row)
+// De-emphasis and arbitrary-rate resampler over bank rows (ldsp.h): float32[nchan, K]
+// -> float32[nchan, nout] (int16 with pcm16).  A device tensor whose columns are
+// one sample apart and whose rows do not overlap (an FMBank output, a block of
+// rows or a range of columns of one) is read in place.
+struct AudioBank {
+    ldsp_audiobank_t q = nullptr;
+    unsigned C = 0, m = 0, npfb = 0;
+    float rate;
+    bool pcm;
+    AudioBank(int nchan, float rate_, int len, const py::object& fc, float as, int nfilter, const py::object& deemph,
+              double tau, bool pcm16)
+        : rate(rate_), pcm(pcm16)
+    {
+        if (nchan < 0) throw py::value_error("AudioBank: nchan must lie in 1 .. 256");
+        if (len < 0) throw py::value_error("AudioBank: len must be >= 1");
+        if (nfilter < 0) throw py::value_error("AudioBank: nfilter must be >= 1");
+        const float c = fc.is_none() ? (float)(0.45 * (double)std::min(rate, 1.0f)) : fc.cast<float>();
+        float sr = 0.0f;
+        if (!deemph.is_none()) {
+            sr = deemph.cast<float>();
+            if (!(sr > 0.0f)) throw py::value_error("AudioBank: deemphasis (the rows' sample rate) must be > 0");
+        }
+        check(ldsp_audiobank_create((unsigned)nchan, rate, (unsigned)len, c, as, (unsigned)nfilter, sr, tau,
+                                    pcm16 ? 1 : 0, &q));
+        m = (unsigned)len;
+        check(ldsp_audiobank_get_info(q, &C, &npfb, nullptr, nullptr, nullptr));
+    }
+    AudioBank(const AudioBank&) = delete;
+    ~AudioBank()
+    {
+        if (q) ldsp_audiobank_destroy(q);
+    }
+    void reset() { check(ldsp_audiobank_reset(q)); }
+    uint32_t step()
+    {
+        uint32_t v;
+        check(ldsp_audiobank_get_info(q, nullptr, nullptr, &v, nullptr, nullptr));
+        return v;
+    }
+    uint32_t phase()
+    {
+        uint32_t v;
+        check(ldsp_audiobank_get_info(q, nullptr, nullptr, nullptr, &v, nullptr));
+        return v;
+    }
+    py::array_t<float> taps()
+    {
+        unsigned n = 0;
+        check(ldsp_audiobank_get_taps(q, nullptr, 0, &n));
+        py::array_t<float> h(n);
+        check(ldsp_audiobank_get_taps(q, h.mutable_data(), n, nullptr));
+        return h;
+    }
+    py::object deemphasis()
+    {
+        float sr;
+        check(ldsp_audiobank_get_coefs(q, nullptr, nullptr, &sr, nullptr));
+        return sr > 0.0f ? py::object(py::float_(sr)) : py::object(py::none());
+    }
+    double tau()
+    {
+        double t;
+        check(ldsp_audiobank_get_coefs(q, nullptr, nullptr, nullptr, &t));
+        return t;
+    }
+    py::tuple coefs()
+    {
+        py::array_t<float> c(2);
+        check(ldsp_audiobank_get_coefs(q, c.mutable_data(), c.mutable_data() + 1, nullptr, nullptr));
+        return py::make_tuple(c[py::int_(0)], c[py::int_(1)]);
+    }
+    float get_scale()
+    {
+        float s;
+        check(ldsp_audiobank_get_scale(q, &s));
+        return s;
+    }
+    void set_scale(float s) { check(ldsp_audiobank_set_scale(q, s)); }
+    size_t tile()
+    {
+        size_t t = 0;
+        check(ldsp_debug_audiobank_tile(q, &t));
+        return t;
+    }
+    size_t num_outputs(size_t K)
+    {
+        size_t c = 0;
+        check(ldsp_audiobank_num_outputs(q, K, &c));
+        return c;
+    }
+    void check_rows(py::ssize_t ndim, py::ssize_t rows) const
+    {
+        if (ndim != 2) throw py::value_error("AudioBank: the input must be 2-D, [nchan, K] (1-D when nchan is 1)");
+        if (rows != (py::ssize_t)C)
+            throw py::value_error("AudioBank: the input has " + std::to_string(rows) + " rows, nchan is " +
+                                  std::to_string(C));
+    }
+    py::object call(const py::handle& x)
+    {
+        size_t nw = 0;
+        if (is_device_tensor(x)) {
+            py::object& torch = torch_mod();
+            py::object t = py::reinterpret_borrow<py::object>(x);
+            if (C == 1 && t.attr("dim")().cast<int>() == 1) t = t.attr("unsqueeze")(0);
+            check_rows(t.attr("dim")().cast<py::ssize_t>(), t.attr("dim")().cast<int>() == 2
+                                                                ? t.attr("size")(0).cast<py::ssize_t>()
+                                                                : 0);
+            if (!py::object(t.attr("dtype")).equal(torch.attr("float32"))) t = t.attr("to")(torch.attr("float32"));
+            const size_t K = t.attr("size")(1).cast<size_t>();
+            // read in place: columns one sample apart, rows that do not overlap
+            if (K > 1 && t.attr("stride")(1).cast<long>() != 1)
+                throw py::value_error("AudioBank: the input's columns must be one sample apart (stride(1) == 1)");
+            if (C > 1 && t.attr("stride")(0).cast<long>() < (long)K)
+                throw py::value_error("AudioBank: the input's row stride must be at least its number of columns");
+            const size_t ldx = C > 1 ? t.attr("stride")(0).cast<size_t>() : K;
+            py::object device = t.attr("device");
+            const int tdev = device.attr("index").cast<int>();
+            const int cur = torch.attr("cuda").attr("current_device")().cast<int>();
+            if (tdev != cur)
+                throw py::value_error("input tensor is on cuda:" + std::to_string(tdev) +
+                                      " but the current device is cuda:" + std::to_string(cur) +
+                                      " (call under torch.cuda.device(" + std::to_string(tdev) + "))");
+            void* stream = reinterpret_cast<void*>(
+                torch.attr("cuda").attr("current_stream")(device).attr("cuda_stream").cast<uintptr_t>());
+            const size_t N = num_outputs(K);
+            py::dict kw;
+            kw["dtype"] = pcm ? torch.attr("int16") : torch.attr("float32");
+            kw["device"] = device;
+            py::object out = torch.attr("empty")(py::make_tuple(C, N), **kw);
+            check(ldsp_audiobank_execute(q, tptr(t), ldx, K, tptr(out), N, &nw, LDSP_MEM_DEVICE, stream));
+            return out;
+        }
+        farr a = farr::ensure(x);
+        if (!a) throw py::error_already_set();
+        if (C == 1 && a.ndim() == 1) a = a.reshape({(py::ssize_t)1, a.shape(0)});
+        check_rows(a.ndim(), a.ndim() == 2 ? a.shape(0) : 0);
+        const size_t K = (size_t)a.shape(1);
+        const size_t N = num_outputs(K);
+        py::array out = pcm ? py::array(py::array_t<int16_t>({(py::ssize_t)C, (py::ssize_t)N}))
+                            : py::array(py::array_t<float>({(py::ssize_t)C, (py::ssize_t)N}));
+        void* yp = out.mutable_data();
+        const void* xp = a.data();
+        int rc;
+        {
+            py::gil_scoped_release rel;
+            rc = ldsp_audiobank_execute(q, xp, K, K, yp, N, &nw, LDSP_MEM_HOST, nullptr);
+        }
+        check(rc);
+        return out;
+    }
+};
+
 // ------------------------------------------------------------------ Synthesizer (no reference counterpart)
 // Polyphase synthesis bank (ldsp.h): complex64[nchan, K] -> complex64[K * interp],
 // row k mixed up to k / nchan.  A device tensor whose columns are contiguous (a
@@ -2144,6 +2297,30 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def_property_readonly("skip", &FMBank::skip, "input samples per row before the next call's first output")
         .def_property_readonly("tile", &FMBank::tile, "output columns per workgroup of the kernel")
         .def("__call__", &FMBank::call, "complex64[nchan, K] -> float32[nchan, ncols]");
+
+    // ---- AudioBank (beyond the reference: de-emphasis and resampler over bank rows)
+    py::class_<AudioBank>(m, "AudioBank")
+        .def(py::init<int, float, int, py::object, float, int, py::object, double, bool>(), py::arg("nchan"),
+             py::arg("rate"), py::arg("len") = 20, py::arg("Fc") = py::none(), py::arg("As") = 60.0f,
+             py::arg("nfilter") = 13, py::arg("deemphasis") = py::none(), py::arg("tau") = 75e-6,
+             py::arg("pcm16") = false)
+        .def("reset", &AudioBank::reset)
+        .def("num_outputs", &AudioBank::num_outputs, py::arg("K"),
+             "outputs per row the next call returns for K input samples per row")
+        .def_property_readonly("nchan", [](AudioBank& c) { return c.C; })
+        .def_property_readonly("rate", [](AudioBank& c) { return c.rate; })
+        .def_property_readonly("len", [](AudioBank& c) { return c.m; })
+        .def_property_readonly("nfilter", [](AudioBank& c) { return c.npfb; }, "after liquid's rounding to a power of two")
+        .def_property_readonly("step", &AudioBank::step)
+        .def_property_readonly("phase", &AudioBank::phase)
+        .def_property_readonly("taps", &AudioBank::taps, "the prototype, 2 len nfilter + 1 taps")
+        .def_property_readonly("deemphasis", &AudioBank::deemphasis, "the rows' sample rate in Hz; None: no de-emphasis")
+        .def_property_readonly("tau", &AudioBank::tau)
+        .def_property_readonly("coefs", &AudioBank::coefs, "(b0, a) of the de-emphasis as float32")
+        .def_property_readonly("pcm16", [](AudioBank& c) { return c.pcm; })
+        .def_property("scale", &AudioBank::get_scale, &AudioBank::set_scale)
+        .def_property_readonly("tile", &AudioBank::tile, "outputs per workgroup of the kernel")
+        .def("__call__", &AudioBank::call, "float32[nchan, K] -> float32[nchan, nout] (int16 with pcm16)");
 
     // ---- Synthesizer (beyond the reference: polyphase synthesis filter bank)
     py::class_<Synthesizer>(m, "Synthesizer")
