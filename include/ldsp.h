@@ -547,6 +547,15 @@ int ldsp_chan_set_scale(ldsp_chan_t q, float s);
 int ldsp_chan_num_outputs(ldsp_chan_t q, size_t n, size_t *ncols);
 int ldsp_chan_execute(ldsp_chan_t q, const void *x, size_t n, void *y, size_t ld, size_t *ncols, int mem,
                       void *stream);
+/* ldsp_bytes_to_iq fused into the bank's loads: x holds n native int16 (I, Q)
+ * pairs (4 n bytes, 4-byte aligned; n counts pairs), each converted to
+ * (float)v / 32767.0f as bytes_to_iq does.  Everything else is
+ * ldsp_chan_execute's: the same checks, *ncols and rows, the bits of
+ * ldsp_bytes_to_iq followed by ldsp_chan_execute, and the same state after the
+ * call (the history is kept as complex64), so the calls of one stream may be of
+ * either kind.  A host input stages 4 n bytes. */
+int ldsp_chan_execute_iq16(ldsp_chan_t q, const void *x, size_t n, void *y, size_t ld, size_t *ncols, int mem,
+                           void *stream);
 /* Test hook: output frames (columns) per workgroup of the (M, D) kernel. */
 int ldsp_debug_chan_tile(unsigned int M, unsigned int D, size_t *frames);
 
@@ -645,6 +654,13 @@ int ldsp_ddc_set_scale(ldsp_ddc_t q, float s);
 int ldsp_ddc_num_outputs(ldsp_ddc_t q, size_t n, size_t *ncols);
 int ldsp_ddc_execute(ldsp_ddc_t q, const void *x, size_t n, void *y, size_t ld, size_t *ncols, int mem,
                      void *stream);
+/* ldsp_bytes_to_iq fused into the bank's loads, as ldsp_chan_execute_iq16: x
+ * holds n native int16 (I, Q) pairs (4 n bytes, 4-byte aligned); the checks,
+ * *ncols, the rows' bits and the state after the call are those of
+ * ldsp_bytes_to_iq followed by ldsp_ddc_execute (the history holds the
+ * converted samples, so retuning and mixed call kinds work as before). */
+int ldsp_ddc_execute_iq16(ldsp_ddc_t q, const void *x, size_t n, void *y, size_t ld, size_t *ncols, int mem,
+                          void *stream);
 /* Test hook: output columns per workgroup of the (D, L) kernel. */
 int ldsp_debug_ddc_tile(unsigned int D, unsigned int L, size_t *frames);
 /* Test hook: reset, then place the stream at sample T (zero history), to reach
@@ -816,6 +832,12 @@ int ldsp_spgram_get_window(ldsp_spgram_t q, float *w);           /* W floats */
 int ldsp_spgram_num_outputs(ldsp_spgram_t q, size_t n, size_t *ntransforms, size_t *nrows);
 int ldsp_spgram_execute(ldsp_spgram_t q, const void *x, size_t n, float *y, size_t ld, size_t *nrows, int mem,
                         void *stream);
+/* ldsp_bytes_to_iq fused into the transform's loads, as ldsp_chan_execute_iq16:
+ * x holds n native int16 (I, Q) pairs (4 n bytes, 4-byte aligned); the checks,
+ * *nrows, the rows, the accumulator's bits and the state after the call are
+ * those of ldsp_bytes_to_iq followed by ldsp_spgram_execute. */
+int ldsp_spgram_execute_iq16(ldsp_spgram_t q, const void *x, size_t n, float *y, size_t ld, size_t *nrows, int mem,
+                             void *stream);
 int ldsp_spgram_get_psd(ldsp_spgram_t q, double *psd, uint64_t *transforms);
 /* Test hook: transforms per workgroup of the nfft kernel (at A > 1: whole rows, at least one). */
 int ldsp_debug_spgram_tile(unsigned int nfft, size_t *transforms);

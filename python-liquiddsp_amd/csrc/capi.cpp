@@ -3480,9 +3480,10 @@ int ldsp_chan_num_outputs(ldsp_chan_t q, size_t n, size_t* ncols)
         *ncols = q->num_outputs(n);
     });
 }
-int ldsp_chan_execute(ldsp_chan_t q, const void* x, size_t n, void* y, size_t ld, size_t* ncols, int mem, void* stream)
+// iq16: x is n int16 (I, Q) pairs (bytes_to_iq's input), converted by the kernel's loads
+static int chan_execute(ldsp_chan_t q, const void* x, size_t n, void* y, size_t ld, size_t* ncols, int mem, void* stream,
+                        bool iq16)
 {
-    LDSP_RANGE("ldsp_chan_execute");
     return guard([&] {
         NONNULL(q);
         const size_t K = q->num_outputs(n);
@@ -3496,7 +3497,7 @@ int ldsp_chan_execute(ldsp_chan_t q, const void* x, size_t n, void* y, size_t ld
         // a host-memory call computes into a dense [M][K] device image
         // (rows of the caller's image are ld samples apart)
         const size_t dld = e.host ? K : ld;
-        const void* dx = q->stg.dev_in(e, x, n * 8);
+        const void* dx = q->stg.dev_in(e, x, n * (iq16 ? 4 : 8));
         void* dy = q->stg.dev_out(e, y, (size_t)M * K * 8);
         if (n > 0) {
             k::ChanCall c;
@@ -3513,6 +3514,7 @@ int ldsp_chan_execute(ldsp_chan_t q, const void* x, size_t n, void* y, size_t ld
             c.tw = q->dtw.p;
             c.scale = q->scale;
             c.y = dy;
+            c.iq16 = iq16;
             k::chan((int)M, (int)D, c, e.stream);
             q->hist.flip();
             q->seen += n;
@@ -3520,6 +3522,17 @@ int ldsp_chan_execute(ldsp_chan_t q, const void* x, size_t n, void* y, size_t ld
         call.end();
         q->stg.finish(e, y, K * 8, M, ld * 8);
     });
+}
+int ldsp_chan_execute(ldsp_chan_t q, const void* x, size_t n, void* y, size_t ld, size_t* ncols, int mem, void* stream)
+{
+    LDSP_RANGE("ldsp_chan_execute");
+    return chan_execute(q, x, n, y, ld, ncols, mem, stream, false);
+}
+int ldsp_chan_execute_iq16(ldsp_chan_t q, const void* x, size_t n, void* y, size_t ld, size_t* ncols, int mem,
+                           void* stream)
+{
+    LDSP_RANGE("ldsp_chan_execute_iq16");
+    return chan_execute(q, x, n, y, ld, ncols, mem, stream, true);
 }
 int ldsp_debug_chan_tile(unsigned int M, unsigned int D, size_t* frames)
 {
@@ -3742,9 +3755,10 @@ int ldsp_ddc_num_outputs(ldsp_ddc_t q, size_t n, size_t* ncols)
         *ncols = q->num_outputs(n);
     });
 }
-int ldsp_ddc_execute(ldsp_ddc_t q, const void* x, size_t n, void* y, size_t ld, size_t* ncols, int mem, void* stream)
+// iq16: x is n int16 (I, Q) pairs (bytes_to_iq's input), converted by the kernel's loads
+static int ddc_execute(ldsp_ddc_t q, const void* x, size_t n, void* y, size_t ld, size_t* ncols, int mem, void* stream,
+                       bool iq16)
 {
-    LDSP_RANGE("ldsp_ddc_execute");
     return guard([&] {
         NONNULL(q);
         const size_t K = q->num_outputs(n);
@@ -3758,7 +3772,7 @@ int ldsp_ddc_execute(ldsp_ddc_t q, const void* x, size_t n, void* y, size_t ld, 
         // a host-memory call computes into a dense [C][K] device image
         // (rows of the caller's image are ld samples apart)
         const size_t dld = e.host ? K : ld;
-        const void* dx = q->stg.dev_in(e, x, n * 8);
+        const void* dx = q->stg.dev_in(e, x, n * (iq16 ? 4 : 8));
         void* dy = q->stg.dev_out(e, y, C * K * 8);
         if (n > 0) {
             k::DdcCall c;
@@ -3777,6 +3791,7 @@ int ldsp_ddc_execute(ldsp_ddc_t q, const void* x, size_t n, void* y, size_t ld, 
             c.words = q->dwords.as<uint32_t>();
             c.scale = q->scale;
             c.y = dy;
+            c.iq16 = iq16;
             k::ddc((int)q->D, c, e.stream);
             q->hist.flip();
             q->seen += n;
@@ -3784,6 +3799,17 @@ int ldsp_ddc_execute(ldsp_ddc_t q, const void* x, size_t n, void* y, size_t ld, 
         call.end();
         q->stg.finish(e, y, K * 8, C, ld * 8);
     });
+}
+int ldsp_ddc_execute(ldsp_ddc_t q, const void* x, size_t n, void* y, size_t ld, size_t* ncols, int mem, void* stream)
+{
+    LDSP_RANGE("ldsp_ddc_execute");
+    return ddc_execute(q, x, n, y, ld, ncols, mem, stream, false);
+}
+int ldsp_ddc_execute_iq16(ldsp_ddc_t q, const void* x, size_t n, void* y, size_t ld, size_t* ncols, int mem,
+                          void* stream)
+{
+    LDSP_RANGE("ldsp_ddc_execute_iq16");
+    return ddc_execute(q, x, n, y, ld, ncols, mem, stream, true);
 }
 int ldsp_debug_ddc_tile(unsigned int D, unsigned int L, size_t* frames)
 {
@@ -4230,7 +4256,8 @@ int ldsp_spgram_num_outputs(ldsp_spgram_t q, size_t n, size_t* ntransforms, size
     });
 }
 // One piece of a call: launches, then the host-side state moves on.
-static void spgram_piece(ldsp_spgram_s* q, const void* dx, size_t n, float* dy, size_t dld, hipStream_t stream)
+static void spgram_piece(ldsp_spgram_s* q, const void* dx, size_t n, float* dy, size_t dld, hipStream_t stream,
+                         bool iq16)
 {
     const unsigned N = q->N;
     const bool blocked = k::spgram_blocked(q->A);
@@ -4259,6 +4286,7 @@ static void spgram_piece(ldsp_spgram_s* q, const void* dx, size_t n, float* dy, 
     const size_t runs = k::spgram_runs((int)N, c.A, c.a0, nt, nullptr);
     c.part = (float*)q->part.ensure(std::max<size_t>(runs, 1) * N * 4, q->device);
     c.psd = q->dpsd.as<double>();
+    c.iq16 = iq16;
     k::spgram((int)N, c, stream);
     q->hist.flip();
     // the unfinished row (block) moved to the other buffer if the piece left one behind
@@ -4271,10 +4299,10 @@ static void spgram_piece(ldsp_spgram_s* q, const void* dx, size_t n, float* dy, 
     q->seen += n;
     q->nacc += nt;
 }
-int ldsp_spgram_execute(ldsp_spgram_t q, const void* x, size_t n, float* y, size_t ld, size_t* nrows, int mem,
-                        void* stream)
+// iq16: x is n int16 (I, Q) pairs (bytes_to_iq's input), converted by the kernel's loads
+static int spgram_execute(ldsp_spgram_t q, const void* x, size_t n, float* y, size_t ld, size_t* nrows, int mem,
+                          void* stream, bool iq16)
 {
-    LDSP_RANGE("ldsp_spgram_execute");
     return guard([&] {
         NONNULL(q);
         const size_t K = q->rows(n);
@@ -4289,7 +4317,8 @@ int ldsp_spgram_execute(ldsp_spgram_t q, const void* x, size_t n, float* y, size
         // (rows of the caller's image are ld floats apart)
         const bool rows_out = y != nullptr && K > 0;
         const size_t dld = e.host ? N : ld;
-        const void* dx = q->stg.dev_in(e, x, n * 8);
+        const size_t xsz = iq16 ? 4 : 8;      // bytes per input sample
+        const void* dx = q->stg.dev_in(e, x, n * xsz);
         float* const dy0 = rows_out ? (float*)q->stg.dev_out(e, y, K * (size_t)N * 4) : nullptr;
         float* dy = dy0;
         // a blocked average is taken in pieces of at most kSpgramMaxBlocks blocks
@@ -4300,13 +4329,25 @@ int ldsp_spgram_execute(ldsp_spgram_t q, const void* x, size_t n, float* y, size
         for (size_t off = 0; off < n;) {
             const size_t m = std::min(n - off, piece);
             const size_t done = q->rows(m);
-            spgram_piece(q, (const char*)dx + off * 8, m, dy, dld, e.stream);
+            spgram_piece(q, (const char*)dx + off * xsz, m, dy, dld, e.stream, iq16);
             if (dy) dy += done * dld;
             off += m;
         }
         call.end();
         q->stg.finish(e, y, (size_t)N * 4, rows_out ? K : 0, ld * 4);
     });
+}
+int ldsp_spgram_execute(ldsp_spgram_t q, const void* x, size_t n, float* y, size_t ld, size_t* nrows, int mem,
+                        void* stream)
+{
+    LDSP_RANGE("ldsp_spgram_execute");
+    return spgram_execute(q, x, n, y, ld, nrows, mem, stream, false);
+}
+int ldsp_spgram_execute_iq16(ldsp_spgram_t q, const void* x, size_t n, float* y, size_t ld, size_t* nrows, int mem,
+                             void* stream)
+{
+    LDSP_RANGE("ldsp_spgram_execute_iq16");
+    return spgram_execute(q, x, n, y, ld, nrows, mem, stream, true);
 }
 int ldsp_spgram_get_psd(ldsp_spgram_t q, double* psd, uint64_t* transforms)
 {

@@ -34,6 +34,9 @@
 #include "chan_dft.hpp"
 #include "kernels.hpp"
 #include "ldsp_common.hpp"
+#include "ldsp_math.hpp"
+
+#include <type_traits>
 
 namespace ldsp {
 namespace k {
@@ -49,12 +52,17 @@ constexpr int chan_slots(int M, int D)
 
 // n: input samples of the call (> 0); skip: samples before the call's first
 // frame; ncols: its frames; par: parity of the first frame's absolute index.
-template <int M, int D>
-__global__ void __launch_bounds__(256) k_chan(const float2* __restrict__ x, const float2* __restrict__ hist,
-                                              float2* __restrict__ hist_out, long n, int skip, long ncols, int par,
-                                              const float* __restrict__ taps, int P, const float2* __restrict__ tw,
-                                              float scale, float2* __restrict__ y, long ld)
+// IQ16: x holds int16 (I, Q) pairs, one 4-byte word per sample, converted where
+// they are loaded (iq_sample); the history stays complex64, so the calls of one
+// stream may be of either kind.
+template <int M, int D, bool IQ16>
+__global__ void __launch_bounds__(256) k_chan(const std::conditional_t<IQ16, int, float2>* __restrict__ x,
+                                              const float2* __restrict__ hist, float2* __restrict__ hist_out, long n,
+                                              int skip, long ncols, int par, const float* __restrict__ taps, int P,
+                                              const float2* __restrict__ tw, float scale, float2* __restrict__ y,
+                                              long ld)
 {
+    using X = std::conditional_t<IQ16, int, float2>;
     constexpr int F = chan_frames(M);
     constexpr int G = 256 / M;                        // frames summed side by side
     constexpr int NF = F / G;                         // frames per thread in the sums
@@ -70,7 +78,8 @@ __global__ void __launch_bounds__(256) k_chan(const float2* __restrict__ x, cons
     if (blockIdx.x == 0) {                            // the next call's history
         for (int j = tid; j < H; j += 256) {
             const long g = n - H + j;
-            hist_out[j] = g < 0 ? hist[g + H] : x[g];
+            if constexpr (IQ16) hist_out[j] = g < 0 ? hist[g + H] : iq_sample(x[g]);
+            else hist_out[j] = g < 0 ? hist[g + H] : x[g];
         }
     }
     if (cnt <= 0) return;                             // a call shorter than skip: workgroup 0 alone, history only
@@ -86,13 +95,19 @@ __global__ void __launch_bounds__(256) k_chan(const float2* __restrict__ x, cons
     if (g0 >= 0 && g0 + span <= n) {
         // an inner tile reads the input alone: all its loads are issued before the first LDS store
         constexpr int kLd = ((F - 1) * D + kChanMaxP * M + 255) / 256;
-        const float2* __restrict__ xb = x + g0;
+        const X* __restrict__ xb = x + g0;
         float2 v[kLd];
 #pragma unroll
         for (int i = 0; i < kLd; i++) {
             const int u = tid + 256 * i;
-            v[i] = make_float2(0.0f, 0.0f);
-            if (u < span) v[i] = xb[u];
+            if constexpr (IQ16) {
+                // no guard round the conversion (it would wait for each load in turn):
+                // lanes past the span load its last word again and store nothing
+                v[i] = iq_sample(xb[min(u, span - 1)]);
+            } else {
+                v[i] = make_float2(0.0f, 0.0f);
+                if (u < span) v[i] = xb[u];
+            }
         }
 #pragma unroll
         for (int i = 0; i < kLd; i++) {
@@ -106,7 +121,7 @@ __global__ void __launch_bounds__(256) k_chan(const float2* __restrict__ x, cons
             if (s < 0) {
                 if (s + H >= 0) v = hist[s + H];
             } else if (s < n) {
-                v = x[s];
+                v = iq_sample(x[s]);
             }
             S[i] = v;
         }
@@ -178,14 +193,21 @@ __global__ void __launch_bounds__(256) k_chan(const float2* __restrict__ x, cons
     }
 }
 
-template <int M, int D>
+template <int M, int D, bool IQ16>
 void chan_launch(const ChanCall& c, hipStream_t s)
 {
     constexpr int F = chan_frames(M);
     const unsigned grid = (unsigned)std::max<size_t>((c.ncols + F - 1) / F, 1);
-    hipLaunchKernelGGL((k_chan<M, D>), dim3(grid), dim3(256), 0, s, (const float2*)c.x, (const float2*)c.hist,
-                       (float2*)c.hist_out, (long)c.n, (int)c.skip, (long)c.ncols, c.parity, c.taps, c.P,
-                       (const float2*)c.tw, c.scale, (float2*)c.y, (long)c.ld);
+    hipLaunchKernelGGL((k_chan<M, D, IQ16>), dim3(grid), dim3(256), 0, s,
+                       (const std::conditional_t<IQ16, int, float2>*)c.x, (const float2*)c.hist, (float2*)c.hist_out,
+                       (long)c.n, (int)c.skip, (long)c.ncols, c.parity, c.taps, c.P, (const float2*)c.tw, c.scale,
+                       (float2*)c.y, (long)c.ld);
+}
+template <int M, int D>
+void chan_launch(const ChanCall& c, hipStream_t s)
+{
+    if (c.iq16) chan_launch<M, D, true>(c, s);
+    else chan_launch<M, D, false>(c, s);
 }
 
 } // namespace

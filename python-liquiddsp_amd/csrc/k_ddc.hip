@@ -39,6 +39,9 @@
 // of history ++ input) into the other buffer of the pair.
 #include "kernels.hpp"
 #include "ldsp_common.hpp"
+#include "ldsp_math.hpp"
+
+#include <type_traits>
 
 namespace ldsp {
 namespace k {
@@ -69,12 +72,16 @@ __device__ __forceinline__ void ddc_mac(float2& a, const float2 g, const float2 
     a.y = fmaf(g.y, v.x, a.y);
 }
 
-template <int TB>
+// IQ16: x holds int16 (I, Q) pairs, one 4-byte word per sample, converted where
+// they are loaded (iq_sample); the history stays complex64, so the calls of one
+// stream may be of either kind.
+template <int TB, bool IQ16>
 __global__ void __launch_bounds__(kDdcThreads)
-    k_ddc(const DdcArgs a, const float2* __restrict__ x, const float2* __restrict__ hist, float2* __restrict__ hist_out,
-          const float2* __restrict__ taps, const int* __restrict__ slots, const uint32_t* __restrict__ words,
-          float2* __restrict__ y)
+    k_ddc(const DdcArgs a, const std::conditional_t<IQ16, int, float2>* __restrict__ x, const float2* __restrict__ hist,
+          float2* __restrict__ hist_out, const float2* __restrict__ taps, const int* __restrict__ slots,
+          const uint32_t* __restrict__ words, float2* __restrict__ y)
 {
+    using X = std::conditional_t<IQ16, int, float2>;
     extern __shared__ __attribute__((aligned(16))) float2 S[];
     const int tid = threadIdx.x;
     const int D = a.D, L = a.L, F = a.F, ROW = a.ROW, H = L - 1;
@@ -86,7 +93,8 @@ __global__ void __launch_bounds__(kDdcThreads)
     if (blockIdx.x == 0) {                            // the next call's history
         for (int j = tid; j < H; j += kDdcThreads) {
             const long g = n - H + j;
-            hist_out[j] = g < 0 ? hist[g + H] : x[g];
+            if constexpr (IQ16) hist_out[j] = g < 0 ? hist[g + H] : iq_sample(x[g]);
+            else hist_out[j] = g < 0 ? hist[g + H] : x[g];
         }
     }
     if (cnt <= 0) return;                             // a call shorter than skip: workgroup 0 alone, history only
@@ -95,11 +103,11 @@ __global__ void __launch_bounds__(kDdcThreads)
     const long g0 = a.skip + c0 * D - H;
     const int span = (F - 1) * D + L;
     if (g0 >= 0 && g0 + span <= n) {                  // an inner tile reads the input alone
-        const float2* __restrict__ xb = x + g0;
+        const X* __restrict__ xb = x + g0;
 #pragma unroll 4
         for (int i = tid; i < span; i += kDdcThreads) {
             const int q = (int)__umulhi((unsigned)i, a.magic);
-            S[(i - q * D) * ROW + q] = xb[i];
+            S[(i - q * D) * ROW + q] = iq_sample(xb[i]);
         }
     } else {
         for (int i = tid; i < span; i += kDdcThreads) {
@@ -108,7 +116,7 @@ __global__ void __launch_bounds__(kDdcThreads)
             if (s < 0) {
                 if (s + H >= 0) v = hist[s + H];
             } else if (s < n) {
-                v = x[s];
+                v = iq_sample(x[s]);
             }
             const int q = (int)__umulhi((unsigned)i, a.magic);
             S[(i - q * D) * ROW + q] = v;
@@ -209,18 +217,25 @@ __global__ void __launch_bounds__(kDdcThreads)
     }
 }
 
-template <int TB>
+template <int TB, bool IQ16>
 void ddc_launch(const DdcArgs& a, const DdcCall& c, size_t lds, hipStream_t s)
 {
     static bool attr = false;     // the largest dynamic LDS any launch may ask for, once per kernel
     if (!attr) {
-        LDSP_HIP(hipFuncSetAttribute((const void*)k_ddc<TB>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        LDSP_HIP(hipFuncSetAttribute((const void*)k_ddc<TB, IQ16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)kDdcLdsMax));
         attr = true;
     }
     const unsigned grid = (unsigned)std::max<long>((a.ncols + a.F - 1) / a.F, 1);
-    hipLaunchKernelGGL((k_ddc<TB>), dim3(grid), dim3(kDdcThreads), lds, s, a, (const float2*)c.x, (const float2*)c.hist,
-                       (float2*)c.hist_out, (const float2*)c.taps, c.slots, c.words, (float2*)c.y);
+    hipLaunchKernelGGL((k_ddc<TB, IQ16>), dim3(grid), dim3(kDdcThreads), lds, s, a,
+                       (const std::conditional_t<IQ16, int, float2>*)c.x, (const float2*)c.hist, (float2*)c.hist_out,
+                       (const float2*)c.taps, c.slots, c.words, (float2*)c.y);
+}
+template <int TB>
+void ddc_launch(const DdcArgs& a, const DdcCall& c, size_t lds, hipStream_t s)
+{
+    if (c.iq16) ddc_launch<TB, true>(a, c, lds, s);
+    else ddc_launch<TB, false>(a, c, lds, s);
 }
 
 } // namespace

@@ -44,11 +44,26 @@
 #include "fft_butterflies.hpp"
 #include "kernels.hpp"
 #include "ldsp_common.hpp"
+#include "ldsp_math.hpp"
+
+#include <type_traits>
+
+// The int16-IQ instantiations are built from this file in a translation unit of
+// their own (k_spgram_iq16.hip defines LDSP_SPGRAM_IQ16): a second set of
+// kernels beside the complex64 ones moves their LDS arrays and, with that, the
+// compiler's schedule of the complex64 code.
+#ifndef LDSP_SPGRAM_IQ16
+#define LDSP_SPGRAM_IQ16 0
+#endif
 
 namespace ldsp {
 namespace k {
 
+void spgram_iq16(int N, const SpgramCall& c, long rg, unsigned grid, hipStream_t s);   // k_spgram_iq16.hip
+
 namespace {
+
+constexpr bool kSpIq16 = LDSP_SPGRAM_IQ16 != 0;
 
 __device__ __forceinline__ int sp_pad(int i) { return i + (i >> 4); }
 __device__ __forceinline__ void sp_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
@@ -139,14 +154,29 @@ __device__ __forceinline__ void sp_fft(float2 (&v)[N / 64], float2* d, const flo
     }
 }
 
-template <int N>
-__global__ void __launch_bounds__(64) k_spgram(const float2* __restrict__ x, const float2* __restrict__ hist,
-                                               float2* __restrict__ hist_out, long n, int W, int d, long A, long a0,
-                                               long nt, long base, long rg, const float* __restrict__ win,
-                                               const float2* __restrict__ tw, const float* __restrict__ carry_in,
-                                               float* __restrict__ carry_out, float inv_a, float* __restrict__ y,
-                                               long ld, float* __restrict__ part)
+// One point of an int16 call's window that may begin in the history: src is the
+// first word of a (complex64) history sample if hist, else the word of an (I, Q)
+// pair.  Without branches: two 4-byte loads, the halves of the history sample
+// or the pair's word twice.
+__device__ __forceinline__ float2 sp_point(const int* src, bool hist)
 {
+    const int lo = src[0], hi = src[hist ? 1 : 0];
+    const float2 c = iq_sample(lo);
+    return hist ? make_float2(bitsf((uint32_t)lo), bitsf((uint32_t)hi)) : c;
+}
+
+// IQ16: x holds int16 (I, Q) pairs, one 4-byte word per sample, converted where
+// they are loaded (iq_sample); the history stays complex64, so the calls of one
+// stream may be of either kind.
+template <int N, bool IQ16>
+__global__ void __launch_bounds__(64) k_spgram(const std::conditional_t<IQ16, int, float2>* __restrict__ x,
+                                               const float2* __restrict__ hist, float2* __restrict__ hist_out, long n,
+                                               int W, int d, long A, long a0, long nt, long base, long rg,
+                                               const float* __restrict__ win, const float2* __restrict__ tw,
+                                               const float* __restrict__ carry_in, float* __restrict__ carry_out,
+                                               float inv_a, float* __restrict__ y, long ld, float* __restrict__ part)
+{
+    using X = std::conditional_t<IQ16, int, float2>;
     constexpr int R = N / 64;
     __shared__ float2 buf[N + N / 16];
     __shared__ float2 ltw[sp_tw_slots(N)];
@@ -155,7 +185,8 @@ __global__ void __launch_bounds__(64) k_spgram(const float2* __restrict__ x, con
     if (blockIdx.x == 0) {                            // the next call's history
         for (int j = lane; j < H; j += 64) {
             const long g = n - H + j;
-            hist_out[j] = g < 0 ? hist[g + H] : x[g];
+            if constexpr (IQ16) hist_out[j] = g < 0 ? hist[g + H] : iq_sample(x[g]);
+            else hist_out[j] = g < 0 ? hist[g + H] : x[g];
         }
     }
     if (nt <= 0) return;                              // a call that takes no transform: history only
@@ -200,11 +231,11 @@ __global__ void __launch_bounds__(64) k_spgram(const float2* __restrict__ x, con
             asm volatile("" : "+v"(ln));
             float2 v[R];
             if (g0 >= 0 && W == N) {                  // no history, no padding
-                const float2* __restrict__ xb = x + g0;
+                const X* __restrict__ xb = x + g0;
 #pragma unroll
                 for (int i = 0; i < R; i++) {
                     const unsigned j = ln + 64u * i;
-                    const float2 e = xb[j];
+                    const float2 e = iq_sample(xb[j]);
                     const float w = WREG ? wv[WREG ? i : 0] : win[j];
                     v[i] = make_float2(e.x * w, e.y * w);
                 }
@@ -215,8 +246,10 @@ __global__ void __launch_bounds__(64) k_spgram(const float2* __restrict__ x, con
                 for (int i = 0; i < R; i++) {
                     const unsigned j = ln + 64u * i;
                     const long g = g0 + min(j, (unsigned)H);
-                    const float2* __restrict__ src = g < 0 ? hist + (g + H) : x + g;
-                    const float2 e = *src;
+                    const X* __restrict__ src = g < 0 ? (const X*)(hist + (g + H)) : x + g;
+                    float2 e;
+                    if constexpr (IQ16) e = sp_point(src, g < 0);
+                    else e = *src;
                     const float w = WREG ? wv[WREG ? i : 0] : win[j];
                     v[i] = j < (unsigned)W ? make_float2(e.x * w, e.y * w) : make_float2(0.0f, 0.0f);
                 }
@@ -255,6 +288,38 @@ __global__ void __launch_bounds__(64) k_spgram(const float2* __restrict__ x, con
     }
 }
 
+template <int N>
+void spgram_launch(const SpgramCall& c, long rg, unsigned grid, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_spgram<N, kSpIq16>), dim3(grid), dim3(64), 0, s,
+                       (const std::conditional_t<kSpIq16, int, float2>*)c.x, (const float2*)c.hist, (float2*)c.hist_out,
+                       (long)c.n, c.W, c.d, (long)c.A, (long)c.a0, (long)c.nt, (long)c.base, rg, c.win,
+                       (const float2*)c.tw, c.carry_in, c.carry_out, c.scale, c.y, (long)c.ld, c.part);
+}
+
+#define LDSP_SPGRAM_CASE(m)                          \
+    case m: {                                        \
+        LDSP_PROF(s, "k_spgram_n" #m);               \
+        spgram_launch<m>(c, rg, grid, s);            \
+    } break
+
+// the main kernel of a call, this translation unit's kind of input
+void spgram_main(int N, const SpgramCall& c, long rg, unsigned grid, hipStream_t s)
+{
+    switch (N) {
+        LDSP_SPGRAM_CASE(256);
+        LDSP_SPGRAM_CASE(512);
+        LDSP_SPGRAM_CASE(1024);
+        LDSP_SPGRAM_CASE(2048);
+        LDSP_SPGRAM_CASE(4096);
+    default:
+        throw Error(LDSP_EINVAL, "spgram: nfft must be a power of two in 256 .. 4096");
+    }
+    LDSP_HIP(hipGetLastError());
+}
+#undef LDSP_SPGRAM_CASE
+
+#if !LDSP_SPGRAM_IQ16
 // psd[k] += sum_b part[b][k]: slice j of 16 adds runs j, j + 16, ... in ascending
 // order, then the slices are added in order.
 constexpr int kSpSlices = 16;
@@ -297,16 +362,13 @@ __global__ void __launch_bounds__(256) k_spgram_rows(const float* __restrict__ b
     }
 }
 
-template <int N>
-void spgram_launch(const SpgramCall& c, long rg, unsigned grid, hipStream_t s)
-{
-    hipLaunchKernelGGL((k_spgram<N>), dim3(grid), dim3(64), 0, s, (const float2*)c.x, (const float2*)c.hist,
-                       (float2*)c.hist_out, (long)c.n, c.W, c.d, (long)c.A, (long)c.a0, (long)c.nt, (long)c.base, rg,
-                       c.win, (const float2*)c.tw, c.carry_in, c.carry_out, c.scale, c.y, (long)c.ld,
-                       c.part);
-}
+#endif
 
 } // namespace
+
+#if LDSP_SPGRAM_IQ16
+void spgram_iq16(int N, const SpgramCall& c, long rg, unsigned grid, hipStream_t s) { spgram_main(N, c, rg, grid, s); }
+#else
 
 size_t spgram_runs(int N, size_t A, size_t a0, size_t nt, size_t* rows_per_run)
 {
@@ -335,12 +397,6 @@ void spgram_rows(int N, const float* blk, size_t nb, size_t M, size_t c0, const 
     LDSP_HIP(hipGetLastError());
 }
 
-#define LDSP_SPGRAM_CASE(m)                          \
-    case m: {                                        \
-        LDSP_PROF(s, "k_spgram_n" #m);               \
-        spgram_launch<m>(c, (long)rg, grid, s);      \
-    } break
-
 void spgram(int N, const SpgramCall& c, hipStream_t s)
 {
     if (c.n == 0) return;
@@ -353,16 +409,8 @@ void spgram(int N, const SpgramCall& c, hipStream_t s)
     size_t rg = 1;
     const size_t runs = spgram_runs(N, c.A, c.a0, c.nt, &rg);
     const unsigned grid = (unsigned)std::max<size_t>(runs, 1);
-    switch (N) {
-        LDSP_SPGRAM_CASE(256);
-        LDSP_SPGRAM_CASE(512);
-        LDSP_SPGRAM_CASE(1024);
-        LDSP_SPGRAM_CASE(2048);
-        LDSP_SPGRAM_CASE(4096);
-    default:
-        throw Error(LDSP_EINVAL, "spgram: nfft must be a power of two in 256 .. 4096");
-    }
-    LDSP_HIP(hipGetLastError());
+    if (c.iq16) spgram_iq16(N, c, (long)rg, grid, s);
+    else spgram_main(N, c, (long)rg, grid, s);
     if (runs > 0) {
         LDSP_PROF(s, "k_spgram_psd");
         hipLaunchKernelGGL(k_spgram_psd, dim3(N / 64), dim3(64 * kSpSlices), 0, s, (const float*)c.part, (long)runs, N,
@@ -370,7 +418,7 @@ void spgram(int N, const SpgramCall& c, hipStream_t s)
         LDSP_HIP(hipGetLastError());
     }
 }
-#undef LDSP_SPGRAM_CASE
+#endif
 
 } // namespace k
 } // namespace ldsp

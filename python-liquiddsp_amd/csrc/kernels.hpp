@@ -386,6 +386,9 @@ void hilbert(int op, const void* x, const void* hist, void* hist_out, size_t n, 
 // The call's frames are at x[skip + c D], c < ncols = ceil((n - skip) / D) (0 when
 // n <= skip); parity: that of the first frame's absolute index (the D = M / 2
 // sign).  y[k * ld + c] receives channel k.  n = 0 launches nothing.
+// iq16 (here, in DdcCall and in SpgramCall): x holds n int16 (I, Q) pairs,
+// 4-byte aligned, converted on load as bytes_to_iq does; hist / hist_out are
+// complex64 either way.
 constexpr int kChanMaxP = 17;
 constexpr int chan_frames(int M) { return M >= 256 ? 32 : 4096 / M; }   // output frames per workgroup
 struct ChanCall {
@@ -398,6 +401,7 @@ struct ChanCall {
     const void* tw;
     float scale;
     void* y;
+    bool iq16 = false;
 };
 void chan(int M, int D, const ChanCall& c, hipStream_t s);
 // k_ddc.hip: tuned decimating filter bank (Downconverter).  C <= kDdcMaxC tuners,
@@ -429,6 +433,7 @@ struct DdcCall {
     const uint32_t* words;
     float scale;
     void* y;
+    bool iq16 = false;
 };
 void ddc(int D, const DdcCall& c, hipStream_t s);
 // k_fmbank.hip: FM discriminator and decimating real FIR over bank rows (FMBank).
@@ -543,6 +548,7 @@ struct SpgramCall {
     float* y;
     float* part;
     double* psd;
+    bool iq16 = false;
 };
 // workgroups (runs of whole rows) a call of nt transforms is cut into: rows of
 // spgram_tile(N) transforms together, more when that would pass kSpgramMaxRuns

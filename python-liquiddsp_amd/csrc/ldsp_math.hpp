@@ -37,6 +37,14 @@ __device__ __forceinline__ float iq16_to_f(short v)
     const float q0 = f * r;
     return fmaf(fmaf(-q0, d, f), r, q0);
 }
+// One input sample as the wideband kernels load it (k_chan, k_ddc, k_spgram):
+// a complex64 as it is, or the 4-byte word of an int16 (I, Q) pair -- I in the
+// low half -- converted as bytes_to_iq does.
+__device__ __forceinline__ float2 iq_sample(float2 v) { return v; }
+__device__ __forceinline__ float2 iq_sample(int w)
+{
+    return make_float2(iq16_to_f((short)(w & 0xffff)), iq16_to_f((short)(w >> 16)));
+}
 
 // e^x (fdlibm e_expf.c): x = k ln2 + r, rational kernel for e^r
 __host__ __device__ inline float lm_expf(float x)

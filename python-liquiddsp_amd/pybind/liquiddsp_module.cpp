@@ -101,6 +101,59 @@ py::object dev_empty(size_t n, bool cplx, const py::object& device)
 
 void* tptr(const py::object& t) { return reinterpret_cast<void*>(t.attr("data_ptr")().cast<uintptr_t>()); }
 
+py::object dev_empty2(size_t rows, size_t cols, bool cplx, const py::object& device)
+{
+    py::object& torch = torch_mod();
+    py::dict kw;
+    kw["dtype"] = cplx ? torch.attr("complex64") : torch.attr("float32");
+    kw["device"] = device;
+    return torch.attr("empty")(py::make_tuple(rows, cols), **kw);
+}
+
+// One call's input where the call reads it: n samples at ptr, on the device
+// (with the stream and device of the tensor) or on the host.
+struct CallIn {
+    py::object keep;    // whatever owns the memory, kept alive for the call
+    const void* ptr = nullptr;
+    size_t n = 0;
+    bool dev = false;
+    void* stream = nullptr;
+    py::object device;
+};
+
+// The input of the from_bytes / write_bytes methods: interleaved int16 (I, Q)
+// pairs as raw bytes -- bytes-like / an int16 or uint8 numpy array (host) or an
+// int16 / uint8 device tensor.  n counts whole pairs: trailing 1-3 bytes are
+// dropped, as bytes_to_iq does (utility.hpp:65 rounds size / 4 down).
+CallIn raw_in(const py::handle& b)
+{
+    CallIn in;
+    if (is_device_tensor(b)) {
+        py::object& torch = torch_mod();
+        py::object t = py::reinterpret_borrow<py::object>(b).attr("reshape")(-1).attr("contiguous")();
+        in.device = t.attr("device");
+        const int tdev = in.device.attr("index").cast<int>();
+        if (tdev != torch.attr("cuda").attr("current_device")().cast<int>())
+            throw py::value_error("input tensor is not on the current device");
+        const size_t nbytes = t.attr("numel")().cast<size_t>() * t.attr("element_size")().cast<size_t>();
+        if (reinterpret_cast<uintptr_t>(tptr(t)) % 4) t = t.attr("clone")();   // a view at an odd offset: the kernels read 4-byte pairs
+        in.ptr = tptr(t);
+        in.n = nbytes / 4;
+        in.dev = true;
+        in.stream = reinterpret_cast<void*>(
+            torch.attr("cuda").attr("current_stream")(in.device).attr("cuda_stream").cast<uintptr_t>());
+        in.keep = t;
+        return in;
+    }
+    py::object o = py::reinterpret_borrow<py::object>(b);
+    if (py::isinstance<py::array>(o)) o = py::module_::import("numpy").attr("ascontiguousarray")(o);
+    py::buffer_info bi = py::reinterpret_borrow<py::buffer>(o).request();
+    in.ptr = bi.ptr;
+    in.n = (size_t)bi.size * (size_t)bi.itemsize / 4;
+    in.keep = o;
+    return in;
+}
+
 // numpy outputs of host-memory calls: page-locked (ldsp_host_alloc) from 64 KB up, so
 // the call DMAs into them and a following call DMAs out of them without a staging
 // copy (the README chain hands each stage's array to the next); ordinary
@@ -119,6 +172,28 @@ py::array host_array(size_t n, bool cplx) { return cplx ? host_array<cf>(n) : ho
 
 using carr = py::array_t<cf, py::array::c_style | py::array::forcecast>;
 using farr = py::array_t<float, py::array::c_style | py::array::forcecast>;
+
+// complex64 input of the same objects' __call__: a device tensor as it is, anything else force-cast
+CallIn cplx_in(const py::handle& x)
+{
+    CallIn in;
+    if (is_device_tensor(x)) {
+        DevIn d = dev_in(x, true);
+        in.keep = d.t;
+        in.ptr = d.ptr;
+        in.n = d.n;
+        in.dev = true;
+        in.stream = d.stream;
+        in.device = d.device;
+        return in;
+    }
+    carr a = carr::ensure(x);
+    if (!a) throw py::error_already_set();
+    in.ptr = a.data();
+    in.n = (size_t)a.size();
+    in.keep = std::move(a);
+    return in;
+}
 
 // Same-length stage (FIR / IIR / NCO / AGC): in -> out of the given kinds
 template <typename F>
@@ -368,35 +443,18 @@ struct IIR {
     py::object from_bytes(const py::handle& b)
     {
         if (!cplx) throw py::value_error("from_bytes: int16 IQ input needs a complex filter");
-        if (is_device_tensor(b)) {
-            py::object& torch = torch_mod();
-            py::object t = py::reinterpret_borrow<py::object>(b).attr("reshape")(-1).attr("contiguous")();
-            py::object dev = t.attr("device");
-            const int tdev = dev.attr("index").cast<int>();
-            if (tdev != torch.attr("cuda").attr("current_device")().cast<int>())
-                throw py::value_error("input tensor is not on the current device");
-            // the tensor's raw bytes, whole (I, Q) pairs only: trailing 1-3 bytes are
-            // dropped, as bytes_to_iq does (utility.hpp:65 rounds size / 4 down)
-            const size_t nbytes = t.attr("numel")().cast<size_t>() * t.attr("element_size")().cast<size_t>();
-            if (reinterpret_cast<uintptr_t>(tptr(t)) % 4) t = t.attr("clone")();   // a view at an odd offset: the kernels read 4-byte pairs
-            const size_t n = nbytes / 4;
-            void* s = reinterpret_cast<void*>(
-                torch.attr("cuda").attr("current_stream")(dev).attr("cuda_stream").cast<uintptr_t>());
-            py::object out = dev_empty(n, true, dev);
-            check(ldsp_iirfilt_execute_iq16(q, tptr(t), n, tptr(out), LDSP_MEM_DEVICE, s));
+        const CallIn in = raw_in(b);
+        if (in.dev) {
+            py::object out = dev_empty(in.n, true, in.device);
+            check(ldsp_iirfilt_execute_iq16(q, in.ptr, in.n, tptr(out), LDSP_MEM_DEVICE, in.stream));
             return out;
         }
-        py::object o = py::reinterpret_borrow<py::object>(b);
-        if (py::isinstance<py::array>(o)) o = py::module_::import("numpy").attr("ascontiguousarray")(o);
-        py::buffer_info bi = py::reinterpret_borrow<py::buffer>(o).request();
-        const size_t nbytes = (size_t)bi.size * (size_t)bi.itemsize;
-        const size_t n = nbytes / 4;                  // trailing 1-3 bytes dropped, as bytes_to_iq
-        py::array_t<cf> out = host_array<cf>(n);
+        py::array_t<cf> out = host_array<cf>(in.n);
         void* yp = out.mutable_data();
         int rc;
         {
             py::gil_scoped_release rel;
-            rc = ldsp_iirfilt_execute_iq16(q, bi.ptr, n, yp, LDSP_MEM_HOST, nullptr);
+            rc = ldsp_iirfilt_execute_iq16(q, in.ptr, in.n, yp, LDSP_MEM_HOST, nullptr);
         }
         check(rc);
         return std::move(out);
@@ -978,35 +1036,30 @@ struct Channelizer {
         check(ldsp_chan_num_outputs(q, n, &c));
         return c;
     }
-    py::object call(const py::handle& x)
+    // iq16: the input is int16 (I, Q) pairs, converted by the kernel's loads (ldsp_chan_execute_iq16)
+    py::object run(const CallIn& in, bool iq16)
     {
+        const auto exec = iq16 ? ldsp_chan_execute_iq16 : ldsp_chan_execute;
         size_t nw = 0;
-        if (is_device_tensor(x)) {
-            DevIn d = dev_in(x, true);
-            const size_t K = num_outputs(d.n);
-            py::object& torch = torch_mod();
-            py::dict kw;
-            kw["dtype"] = torch.attr("complex64");
-            kw["device"] = d.device;
-            py::object out = torch.attr("empty")(py::make_tuple(M, K), **kw);
-            check(ldsp_chan_execute(q, d.ptr, d.n, tptr(out), K, &nw, LDSP_MEM_DEVICE, d.stream));
+        const size_t K = num_outputs(in.n);
+        if (in.dev) {
+            py::object out = dev_empty2(M, K, true, in.device);
+            check(exec(q, in.ptr, in.n, tptr(out), K, &nw, LDSP_MEM_DEVICE, in.stream));
             return out;
         }
-        carr a = carr::ensure(x);
-        if (!a) throw py::error_already_set();
-        const size_t n = (size_t)a.size();
-        const size_t K = num_outputs(n);
         py::array_t<cf> out({(py::ssize_t)M, (py::ssize_t)K});
         void* yp = out.mutable_data();
-        const void* xp = a.data();
         int rc;
         {
             py::gil_scoped_release rel;
-            rc = ldsp_chan_execute(q, xp, n, yp, K, &nw, LDSP_MEM_HOST, nullptr);
+            rc = exec(q, in.ptr, in.n, yp, K, &nw, LDSP_MEM_HOST, nullptr);
         }
         check(rc);
-        return out;
+        return std::move(out);
     }
+    py::object call(const py::handle& x) { return run(cplx_in(x), false); }
+    // self(bytes_to_iq(raw)) without the complex64 copy: raw as ComplexIIRFilter.from_bytes takes it
+    py::object from_bytes(const py::handle& b) { return run(raw_in(b), true); }
 };
 
 // ------------------------------------------------------------------ Downconverter (liquid: nco_crcf + firdecim_crcf)
@@ -1101,36 +1154,31 @@ struct Downconverter {
         return c;
     }
     void seek(uint64_t T) { check(ldsp_debug_ddc_seek(q, T)); }
-    py::object call(const py::handle& x)
+    // iq16: the input is int16 (I, Q) pairs, converted by the kernel's loads (ldsp_ddc_execute_iq16)
+    py::object run(const CallIn& in, bool iq16)
     {
+        const auto exec = iq16 ? ldsp_ddc_execute_iq16 : ldsp_ddc_execute;
         size_t nw = 0;
         const unsigned C = ntuners();
-        if (is_device_tensor(x)) {
-            DevIn d = dev_in(x, true);
-            const size_t K = num_outputs(d.n);
-            py::object& torch = torch_mod();
-            py::dict kw;
-            kw["dtype"] = torch.attr("complex64");
-            kw["device"] = d.device;
-            py::object out = torch.attr("empty")(py::make_tuple(C, K), **kw);
-            check(ldsp_ddc_execute(q, d.ptr, d.n, tptr(out), K, &nw, LDSP_MEM_DEVICE, d.stream));
+        const size_t K = num_outputs(in.n);
+        if (in.dev) {
+            py::object out = dev_empty2(C, K, true, in.device);
+            check(exec(q, in.ptr, in.n, tptr(out), K, &nw, LDSP_MEM_DEVICE, in.stream));
             return out;
         }
-        carr a = carr::ensure(x);
-        if (!a) throw py::error_already_set();
-        const size_t n = (size_t)a.size();
-        const size_t K = num_outputs(n);
         py::array_t<cf> out({(py::ssize_t)C, (py::ssize_t)K});
         void* yp = out.mutable_data();
-        const void* xp = a.data();
         int rc;
         {
             py::gil_scoped_release rel;
-            rc = ldsp_ddc_execute(q, xp, n, yp, K, &nw, LDSP_MEM_HOST, nullptr);
+            rc = exec(q, in.ptr, in.n, yp, K, &nw, LDSP_MEM_HOST, nullptr);
         }
         check(rc);
-        return out;
+        return std::move(out);
     }
+    py::object call(const py::handle& x) { return run(cplx_in(x), false); }
+    // self(bytes_to_iq(raw)) without the complex64 copy: raw as ComplexIIRFilter.from_bytes takes it
+    py::object from_bytes(const py::handle& b) { return run(raw_in(b), true); }
 };
 
 // ------------------------------------------------------------------ FMBank (liquid: freqdem + firdecim_rrrf per row)
@@ -1614,43 +1662,39 @@ struct Spectrogram {
         check(ldsp_spgram_num_outputs(q, n, &t, &r));
         return py::make_tuple(t, r);
     }
-    // rows: store them and return the image; otherwise accumulate only and return the transforms taken
-    py::object run(const py::handle& x, bool rows)
+    // rows: store them and return the image; otherwise accumulate only and return the transforms taken.
+    // iq16: the input is int16 (I, Q) pairs, converted by the kernel's loads (ldsp_spgram_execute_iq16)
+    py::object run(const CallIn& in, bool rows, bool iq16)
     {
+        const auto exec = iq16 ? ldsp_spgram_execute_iq16 : ldsp_spgram_execute;
         size_t nt = 0, K = 0, nw = 0;
-        if (is_device_tensor(x)) {
-            DevIn d = dev_in(x, true);
-            check(ldsp_spgram_num_outputs(q, d.n, &nt, &K));
+        check(ldsp_spgram_num_outputs(q, in.n, &nt, &K));
+        if (in.dev) {
             py::object out;
             float* yp = nullptr;
             if (rows) {
-                py::object& torch = torch_mod();
-                py::dict kw;
-                kw["dtype"] = torch.attr("float32");
-                kw["device"] = d.device;
-                out = torch.attr("empty")(py::make_tuple(K, N), **kw);
+                out = dev_empty2(K, N, false, in.device);
                 yp = (float*)tptr(out);
             }
-            check(ldsp_spgram_execute(q, d.ptr, d.n, yp, N, &nw, LDSP_MEM_DEVICE, d.stream));
+            check(exec(q, in.ptr, in.n, yp, N, &nw, LDSP_MEM_DEVICE, in.stream));
             return rows ? out : py::object(py::int_(nt));
         }
-        carr a = carr::ensure(x);
-        if (!a) throw py::error_already_set();
-        const size_t n = (size_t)a.size();
-        check(ldsp_spgram_num_outputs(q, n, &nt, &K));
         py::array_t<float> out({(py::ssize_t)(rows ? K : 0), (py::ssize_t)N});
         float* yp = rows ? out.mutable_data() : nullptr;
-        const void* xp = a.data();
         int rc;
         {
             py::gil_scoped_release rel;
-            rc = ldsp_spgram_execute(q, xp, n, yp, N, &nw, LDSP_MEM_HOST, nullptr);
+            rc = exec(q, in.ptr, in.n, yp, N, &nw, LDSP_MEM_HOST, nullptr);
         }
         check(rc);
         return rows ? py::object(out) : py::object(py::int_(nt));
     }
-    py::object call(const py::handle& x) { return run(x, true); }
-    py::object write(const py::handle& x) { return run(x, false); }
+    py::object call(const py::handle& x) { return run(cplx_in(x), true, false); }
+    py::object write(const py::handle& x) { return run(cplx_in(x), false, false); }
+    // self(bytes_to_iq(raw)) / self.write(bytes_to_iq(raw)) without the complex64
+    // copy: raw as ComplexIIRFilter.from_bytes takes it
+    py::object from_bytes(const py::handle& b) { return run(raw_in(b), true, true); }
+    py::object write_bytes(const py::handle& b) { return run(raw_in(b), false, true); }
 };
 
 // SSBDemod (demod.hpp:155-187): firhilbf_create(25, 60), c2r, one sideband kept
@@ -2260,6 +2304,8 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def_property_readonly("skip", &Channelizer::skip, "input samples before the next call's first output")
         .def_property_readonly("tile", &Channelizer::tile, "output columns per workgroup of the kernel")
         .def_property_readonly("centers", &Channelizer::centers, "channel centres k / nchan wrapped into [-0.5, 0.5)")
+        .def("from_bytes", &Channelizer::from_bytes, py::arg("byts"),
+             "self(bytes_to_iq(byts)) in one pass: int16 (I, Q) pairs converted on load")
         .def("__call__", &Channelizer::call, "complex64[N] -> complex64[nchan, ncols]");
 
     // ---- Downconverter (liquid: nco_crcf + firdecim_crcf as one bank)
@@ -2279,6 +2325,8 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def_property("scale", &Downconverter::get_scale, &Downconverter::set_scale)
         .def_property_readonly("skip", &Downconverter::skip, "input samples before the next call's first output")
         .def_property_readonly("tile", &Downconverter::tile, "output columns per workgroup of the kernel")
+        .def("from_bytes", &Downconverter::from_bytes, py::arg("byts"),
+             "self(bytes_to_iq(byts)) in one pass: int16 (I, Q) pairs converted on load")
         .def("__call__", &Downconverter::call, "complex64[N] -> complex64[ntuners, ncols]");
 
     // ---- FMBank (beyond the reference: discriminator and decimating FIR over bank rows)
@@ -2346,6 +2394,10 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def("num_outputs", &Spectrogram::num_outputs, py::arg("n"),
              "(transforms, rows) the next call takes / returns for n input samples")
         .def("write", &Spectrogram::write, "accumulate only; returns the transforms taken")
+        .def("from_bytes", &Spectrogram::from_bytes, py::arg("byts"),
+             "self(bytes_to_iq(byts)) in one pass: int16 (I, Q) pairs converted on load")
+        .def("write_bytes", &Spectrogram::write_bytes, py::arg("byts"),
+             "self.write(bytes_to_iq(byts)) in one pass: int16 (I, Q) pairs converted on load")
         .def_property_readonly("nfft", [](Spectrogram& c) { return c.N; })
         .def_property_readonly("window", &Spectrogram::window)
         .def_property_readonly("window_len", [](Spectrogram& c) { return c.W; })
