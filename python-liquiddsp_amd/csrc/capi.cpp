@@ -1250,6 +1250,14 @@ struct ldsp_firhilb_s : ldsp::DevObj {
     }
 };
 
+// Where a decimating T stands in its stream (T::D, T::seen): the samples before the next output, the outputs of n samples
+template <class T>
+struct Decimating {
+    const T& self() const { return static_cast<const T&>(*this); }
+    size_t skip() const { return (size_t)((self().D - self().seen % self().D) % self().D); }
+    size_t num_outputs(size_t n) const { return n > skip() ? (n - skip() + self().D - 1) / self().D : 0; }
+};
+
 // The two polyphase banks: the prototype, the host-side stream position, and
 // on the device the taps padded to kChanMaxP M, the twiddle table
 // exp(2 pi i j / M), j < M, as (re, im) pairs (double, rounded once) and the
@@ -1281,9 +1289,7 @@ struct BankObj : ldsp::DevObj {
 
 // Channelizer (polyphase analysis bank): skip and the output parity follow from
 // the samples seen; the history is the last P M - 1 input samples.
-struct ldsp_chan_s : BankObj {
-    size_t skip() const { return (size_t)((D - seen % D) % D); }
-    size_t num_outputs(size_t n) const { return n > skip() ? (n - skip() + D - 1) / D : 0; }
+struct ldsp_chan_s : BankObj, Decimating<ldsp_chan_s> {
     int parity() const { return (int)(((seen + D - 1) / D) & 1); }   // of the next output's absolute index
 };
 
@@ -1296,7 +1302,7 @@ struct ldsp_synth_s : BankObj {};
 // follow from it), and on the device the complex taps g_c in the kernel's
 // layout (kernels.hpp), the words and the last L - 1 raw input samples,
 // ping-ponged.  The history is raw input, so a retune touches the tables alone.
-struct ldsp_ddc_s : ldsp::DevObj {
+struct ldsp_ddc_s : ldsp::DevObj, Decimating<ldsp_ddc_s> {
     unsigned int D = 0;
     std::vector<float> h;
     std::vector<uint32_t> w;
@@ -1305,8 +1311,6 @@ struct ldsp_ddc_s : ldsp::DevObj {
     ldsp::DevBuf dtaps, dwords, dslots;
     ldsp::PingPong hist;
     size_t hist_bytes() const { return std::max<size_t>(h.size() - 1, 1) * 8; }
-    size_t skip() const { return (size_t)((D - seen % D) % D); }
-    size_t num_outputs(size_t n) const { return n > skip() ? (n - skip() + D - 1) / D : 0; }
     uint64_t next_column() const { return seen / D + (seen % D != 0); }
     // g_c[j] = h[j] exp(+2 pi i ((j w_c) mod 2^32) / 2^32) in double, rounded once, as
     // [tuner block][k = L - 1 - j][TB]; the phase as a signed count of 2^-31 half-turns
@@ -1344,7 +1348,7 @@ struct ldsp_ddc_s : ldsp::DevObj {
 // per row the last L - 1 discriminator values and the last raw sample, both
 // ping-ponged.  The history holds discriminator values, so zeroed buffers are
 // the definition's "d = 0 before t = 0".
-struct ldsp_fmbank_s : ldsp::DevObj {
+struct ldsp_fmbank_s : ldsp::DevObj, Decimating<ldsp_fmbank_s> {
     unsigned int C = 0, D = 1;
     float ref = 0.0f;                      // (float)(1 / (2 pi kf))
     std::vector<float> h;                  // empty: the discriminator alone
@@ -1353,8 +1357,6 @@ struct ldsp_fmbank_s : ldsp::DevObj {
     ldsp::DevBuf dtaps;
     ldsp::PingPong dhist, prev;
     size_t hist_bytes() const { return std::max<size_t>((size_t)C * (h.empty() ? 0 : h.size() - 1), 1) * 4; }
-    size_t skip() const { return (size_t)((D - seen % D) % D); }
-    size_t num_outputs(size_t n) const { return n > skip() ? (n - skip() + D - 1) / D : 0; }
     void zero_state(int dev)
     {
         dhist.zero(hist_bytes(), dev);
@@ -3655,11 +3657,32 @@ static void ddc_check_decim(unsigned int D)
     if (D > (unsigned)k::kDdcMaxD)
         throw Error(LDSP_EUNSUP, "ddc: decimation above " + std::to_string(k::kDdcMaxD) + " is not implemented");
 }
+// The Downconverter's and the FMBank's Kaiser prototype of 2 D m + 1 taps with the scale 1 / their sum (in double);
+// a cutoff that is not positive stands for 0.5 / D, `pre` is the messages' prefix.  D = 1 decimates nothing: no taps.
+static std::pair<std::vector<float>, float> decim_prototype(const std::string& pre, unsigned D, unsigned m, float fc, float as)
+{
+    LDSP_REQUIRE(m >= 1, pre + ": filter semi-length must be at least 1");
+    LDSP_REQUIRE(as > 0.0f, pre + ": stop-band attenuation must be > 0");
+    LDSP_REQUIRE(fc < 0.5f, pre + ": cutoff must be below 0.5");
+    if (2 * (size_t)m + 1 > (size_t)k::kChanMaxP)
+        throw Error(LDSP_EUNSUP, pre + ": semi-length above " + std::to_string((k::kChanMaxP - 1) / 2) +
+                                     " is not implemented");
+    if (D == 1) return {{}, 1.0f};
+    std::vector<float> h = design::firdes_kaiser(2 * D * m + 1, fc > 0.0f ? fc : 0.5f / (float)D, as, 0.0f);
+    double sum = 0.0;
+    for (float v : h) sum += (double)v;
+    return {std::move(h), (float)(1.0 / sum)};
+}
+// At most kChanMaxP taps per output phase; `bound`: with the create functions' "(L > 17 D) "
+static void decim_check_taps(const std::string& pre, size_t L, unsigned D, bool bound)
+{
+    const std::string P = std::to_string(k::kChanMaxP), b = bound ? "(L > " + P + " D) " : "";
+    if (L > (size_t)k::kChanMaxP * D)
+        throw Error(LDSP_EUNSUP, pre + ": more than " + P + " taps per output phase " + b + "is not implemented");
+}
 static ldsp_ddc_s* ddc_make(std::vector<uint32_t> w, unsigned int D, std::vector<float> h, float scale)
 {
-    if (h.size() > (size_t)k::kChanMaxP * D)
-        throw Error(LDSP_EUNSUP, "ddc: more than " + std::to_string(k::kChanMaxP) + " taps per output phase (L > " +
-                                     std::to_string(k::kChanMaxP) + " D) is not implemented");
+    decim_check_taps("ddc", h.size(), D, true);
     std::unique_ptr<ldsp_ddc_s> o(new ldsp_ddc_s());
     o->D = D;
     o->h = std::move(h);
@@ -3673,16 +3696,8 @@ int ldsp_ddc_create(const double* f, unsigned int C, unsigned int D, unsigned in
         NONNULL(q);
         ddc_check_decim(D);
         std::vector<uint32_t> w = ddc_words(f, C);
-        LDSP_REQUIRE(m >= 1, "ddc: filter semi-length must be at least 1");
-        LDSP_REQUIRE(as > 0.0f, "ddc: stop-band attenuation must be > 0");
-        LDSP_REQUIRE(fc < 0.5f, "ddc: cutoff must be below 0.5");
-        if (2 * (size_t)m + 1 > (size_t)k::kChanMaxP)
-            throw Error(LDSP_EUNSUP, "ddc: semi-length above " + std::to_string((k::kChanMaxP - 1) / 2) +
-                                         " is not implemented");
-        std::vector<float> h = design::firdes_kaiser(2 * D * m + 1, fc > 0.0f ? fc : 0.5f / (float)D, as, 0.0f);
-        double sum = 0.0;
-        for (float v : h) sum += (double)v;
-        *q = ddc_make(std::move(w), D, std::move(h), (float)(1.0 / sum));
+        auto p = decim_prototype("ddc", D, m, fc, as);
+        *q = ddc_make(std::move(w), D, std::move(p.first), p.second);
     });
 }
 int ldsp_ddc_create_taps(const double* f, unsigned int C, unsigned int D, const float* h, unsigned int L, ldsp_ddc_t* q)
@@ -3817,7 +3832,7 @@ int ldsp_debug_ddc_tile(unsigned int D, unsigned int L, size_t* frames)
         NONNULL(frames);
         ddc_check_decim(D);
         LDSP_REQUIRE(L >= 1, "ddc: at least one tap");
-        if (L > (unsigned)k::kChanMaxP * D) throw Error(LDSP_EUNSUP, "ddc: more than 17 taps per output phase is not implemented");
+        decim_check_taps("ddc", L, D, false);
         *frames = (size_t)k::ddc_frames((int)D, (int)L);
     });
 }
@@ -3846,20 +3861,8 @@ int ldsp_fmbank_create(unsigned int C, float kf, unsigned int D, unsigned int m,
     return guard([&] {
         NONNULL(q);
         fmbank_check_shape(C, kf, D);
-        LDSP_REQUIRE(m >= 1, "fmbank: filter semi-length must be at least 1");
-        LDSP_REQUIRE(as > 0.0f, "fmbank: stop-band attenuation must be > 0");
-        LDSP_REQUIRE(fc < 0.5f, "fmbank: cutoff must be below 0.5");
-        if (2 * (size_t)m + 1 > (size_t)k::kChanMaxP)
-            throw Error(LDSP_EUNSUP, "fmbank: semi-length above " + std::to_string((k::kChanMaxP - 1) / 2) +
-                                         " is not implemented");
-        if (D == 1) {                                  // nothing to decimate: the discriminator alone
-            *q = fmbank_make(C, kf, D, {}, 1.0f);
-            return;
-        }
-        std::vector<float> h = design::firdes_kaiser(2 * D * m + 1, fc > 0.0f ? fc : 0.5f / (float)D, as, 0.0f);
-        double sum = 0.0;
-        for (float v : h) sum += (double)v;
-        *q = fmbank_make(C, kf, D, std::move(h), (float)(1.0 / sum));
+        auto p = decim_prototype("fmbank", D, m, fc, as);     // D = 1: the discriminator alone
+        *q = fmbank_make(C, kf, D, std::move(p.first), p.second);
     });
 }
 int ldsp_fmbank_create_taps(unsigned int C, float kf, unsigned int D, const float* h, unsigned int L, ldsp_fmbank_t* q)
@@ -3869,9 +3872,7 @@ int ldsp_fmbank_create_taps(unsigned int C, float kf, unsigned int D, const floa
         fmbank_check_shape(C, kf, D);
         LDSP_REQUIRE(L >= 1, "fmbank: at least one tap");
         NONNULL(h);
-        if (L > (unsigned)k::kChanMaxP * D)
-            throw Error(LDSP_EUNSUP, "fmbank: more than " + std::to_string(k::kChanMaxP) + " taps per output phase (L > " +
-                                         std::to_string(k::kChanMaxP) + " D) is not implemented");
+        decim_check_taps("fmbank", L, D, true);
         *q = fmbank_make(C, kf, D, std::vector<float>(h, h + L), 1.0f);
     });
 }
@@ -3971,8 +3972,7 @@ int ldsp_debug_fmbank_tile(unsigned int D, unsigned int L, size_t* frames)
         NONNULL(frames);
         LDSP_REQUIRE(D >= 1 && D <= (unsigned)k::kFmbankMaxD,
                      "fmbank: the decimation must lie in 1 .. " + std::to_string(k::kFmbankMaxD));
-        if (L > (unsigned)k::kChanMaxP * D)
-            throw Error(LDSP_EUNSUP, "fmbank: more than 17 taps per output phase is not implemented");
+        decim_check_taps("fmbank", L, D, false);
         *frames = L == 0 ? 256 : (size_t)k::fmbank_frames((int)D, (int)L);
     });
 }

@@ -58,99 +58,212 @@ bool is_device_tensor(const py::handle& o)
     return o.attr("is_cuda").cast<bool>();
 }
 
-struct DevIn {
-    py::object t;       // contiguous tensor kept alive for the call
-    void* ptr;
-    size_t n;
-    void* stream;
-    py::object device;
-};
-
-DevIn dev_in(const py::handle& x, bool cplx)
-{
-    py::object& torch = torch_mod();
-    py::object want = cplx ? torch.attr("complex64") : torch.attr("float32");
-    py::object t = py::reinterpret_borrow<py::object>(x);
-    if (!py::object(t.attr("dtype")).equal(want)) t = t.attr("to")(want);
-    t = t.attr("reshape")(-1).attr("contiguous")();
-    DevIn d;
-    d.device = t.attr("device");
-    // libldsp binds an object to the current HIP device on first use and
-    // launches there: a tensor on another device would hand it foreign pointers
-    const int tdev = d.device.attr("index").cast<int>();
-    const int cur = torch.attr("cuda").attr("current_device")().cast<int>();
-    if (tdev != cur)
-        throw py::value_error("input tensor is on cuda:" + std::to_string(tdev) + " but the current device is cuda:" +
-                              std::to_string(cur) + " (call under torch.cuda.device(" + std::to_string(tdev) + "))");
-    d.ptr = reinterpret_cast<void*>(t.attr("data_ptr")().cast<uintptr_t>());
-    d.n = t.attr("numel")().cast<size_t>();
-    d.stream = reinterpret_cast<void*>(
-        torch.attr("cuda").attr("current_stream")(d.device).attr("cuda_stream").cast<uintptr_t>());
-    d.t = t;
-    return d;
-}
-
-py::object dev_empty(size_t n, bool cplx, const py::object& device)
-{
-    py::object& torch = torch_mod();
-    py::dict kw;
-    kw["dtype"] = cplx ? torch.attr("complex64") : torch.attr("float32");
-    kw["device"] = device;
-    return torch.attr("empty")(py::int_(n), **kw);
-}
-
 void* tptr(const py::object& t) { return reinterpret_cast<void*>(t.attr("data_ptr")().cast<uintptr_t>()); }
 
-py::object dev_empty2(size_t rows, size_t cols, bool cplx, const py::object& device)
+// ------------------------------------------------------------------ the call scaffold
+// Every call is: build the input (in_1d / in_rows), ask the C ABI for the
+// output size, allocate (make_out), invoke.
+
+// One owner for every C-ABI handle: move-only, destroys on destruction; it
+// stands for the handle wherever a C function takes one.
+template <typename H, int (*Destroy)(H)>
+class Handle {
+    H h = nullptr;
+
+public:
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&& o) noexcept
+    {
+        std::swap(h, o.h);      // o destroys what this held
+        return *this;
+    }
+    ~Handle() { if (h) Destroy(h); }
+    H get() const { return h; }
+    operator H() const { return h; }
+    H* out() { return &h; }     // for the create functions
+};
+
+// float s; check(get(q, &s)); return s;
+template <typename T, typename Q, typename G>
+T get_value(G get, const Q& q)
 {
-    py::object& torch = torch_mod();
-    py::dict kw;
-    kw["dtype"] = cplx ? torch.attr("complex64") : torch.attr("float32");
-    kw["device"] = device;
-    return torch.attr("empty")(py::make_tuple(rows, cols), **kw);
+    T v;
+    check(get(q, &v));
+    return v;
 }
 
-// One call's input where the call reads it: n samples at ptr, on the device
-// (with the stream and device of the tensor) or on the host.
+// The element kinds of inputs and results
+enum class Kind { f32, c64, i16 };
+constexpr Kind kind_of(bool cplx) { return cplx ? Kind::c64 : Kind::f32; }
+const char* torch_name(Kind k) { return k == Kind::c64 ? "complex64" : (k == Kind::f32 ? "float32" : "int16"); }
+size_t kind_size(Kind k) { return k == Kind::c64 ? 8 : (k == Kind::f32 ? 4 : 2); }
+py::dtype np_dtype(Kind k)
+{
+    return k == Kind::c64 ? py::dtype::of<cf>() : (k == Kind::f32 ? py::dtype::of<float>() : py::dtype::of<int16_t>());
+}
+// The dtype dispatch of Delay and HilbertTransform: complex64 or float32, false for anything else
+bool kind_from_dtype(const py::handle& x, Kind* k)
+{
+    py::object tp = py::getattr(x, "dtype");
+    const bool dev = is_device_tensor(x);
+    for (Kind c : {Kind::c64, Kind::f32})
+        if (tp.equal(dev ? py::object(torch_mod().attr(torch_name(c))) : py::object(py::dtype(torch_name(c))))) {
+            *k = c;
+            return true;
+        }
+    return false;
+}
+
+// One call's input where the call reads it: n samples at ptr (a row image: n
+// per row, rows ld samples apart), on the device (with the stream and device
+// of the tensor) or on the host.
 struct CallIn {
     py::object keep;    // whatever owns the memory, kept alive for the call
     const void* ptr = nullptr;
-    size_t n = 0;
+    size_t n = 0, ld = 0;
     bool dev = false;
     void* stream = nullptr;
     py::object device;
 };
 
-// The input of the from_bytes / write_bytes methods: interleaved int16 (I, Q)
-// pairs as raw bytes -- bytes-like / an int16 or uint8 numpy array (host) or an
-// int16 / uint8 device tensor.  n counts whole pairs: trailing 1-3 bytes are
-// dropped, as bytes_to_iq does (utility.hpp:65 rounds size / 4 down).
-CallIn raw_in(const py::handle& b)
+// A device tensor as a call's input: its device, checked against the current
+// one -- libldsp binds an object to the current HIP device on first use and
+// launches there: a tensor on another device would hand it foreign pointers --
+// and torch's current stream on it.
+enum class DevCheck { none, brief, full };
+void on_device(CallIn& in, const py::object& t, DevCheck chk)
+{
+    py::object& torch = torch_mod();
+    in.device = t.attr("device");
+    if (chk != DevCheck::none) {
+        const int tdev = in.device.attr("index").cast<int>();
+        const int cur = torch.attr("cuda").attr("current_device")().cast<int>();
+        if (tdev != cur && chk == DevCheck::brief) throw py::value_error("input tensor is not on the current device");
+        if (tdev != cur)
+            throw py::value_error("input tensor is on cuda:" + std::to_string(tdev) + " but the current device is cuda:" +
+                                  std::to_string(cur) + " (call under torch.cuda.device(" + std::to_string(tdev) + "))");
+    }
+    in.keep = t;
+    in.ptr = tptr(t);
+    in.dev = true;
+    in.stream = reinterpret_cast<void*>(
+        torch.attr("cuda").attr("current_stream")(in.device).attr("cuda_stream").cast<uintptr_t>());
+}
+
+using carr = py::array_t<cf, py::array::c_style | py::array::forcecast>;
+using farr = py::array_t<float, py::array::c_style | py::array::forcecast>;
+
+// x as a contiguous host array of kind k (force-cast)
+py::array host_in(const py::handle& x, Kind k)
+{
+    py::array a = k == Kind::c64 ? py::array(carr::ensure(x)) : py::array(farr::ensure(x));
+    if (!a) throw py::error_already_set();
+    return a;
+}
+py::object dev_cast(const py::handle& x, Kind k)
+{
+    py::object want = torch_mod().attr(torch_name(k));
+    py::object t = py::reinterpret_borrow<py::object>(x);
+    return py::object(t.attr("dtype")).equal(want) ? t : py::object(t.attr("to")(want));
+}
+
+// A 1-D input: a device tensor as it is, anything else force-cast, both
+// flattened.  Kind::i16 is the input of the from_bytes / write_bytes methods:
+// interleaved int16 (I, Q) pairs as raw bytes -- bytes-like / an int16 or uint8
+// numpy array (host) or an int16 / uint8 device tensor.  n then counts whole
+// pairs: trailing 1-3 bytes are dropped, as bytes_to_iq does (utility.hpp:65
+// rounds size / 4 down).
+CallIn in_1d(const py::handle& x, Kind k)
 {
     CallIn in;
-    if (is_device_tensor(b)) {
-        py::object& torch = torch_mod();
-        py::object t = py::reinterpret_borrow<py::object>(b).attr("reshape")(-1).attr("contiguous")();
-        in.device = t.attr("device");
-        const int tdev = in.device.attr("index").cast<int>();
-        if (tdev != torch.attr("cuda").attr("current_device")().cast<int>())
-            throw py::value_error("input tensor is not on the current device");
-        const size_t nbytes = t.attr("numel")().cast<size_t>() * t.attr("element_size")().cast<size_t>();
-        if (reinterpret_cast<uintptr_t>(tptr(t)) % 4) t = t.attr("clone")();   // a view at an odd offset: the kernels read 4-byte pairs
-        in.ptr = tptr(t);
-        in.n = nbytes / 4;
-        in.dev = true;
-        in.stream = reinterpret_cast<void*>(
-            torch.attr("cuda").attr("current_stream")(in.device).attr("cuda_stream").cast<uintptr_t>());
-        in.keep = t;
+    if (k == Kind::i16 && is_device_tensor(x)) {
+        py::object t = py::reinterpret_borrow<py::object>(x).attr("reshape")(-1).attr("contiguous")();
+        on_device(in, t, DevCheck::brief);
+        in.n = t.attr("numel")().cast<size_t>() * t.attr("element_size")().cast<size_t>() / 4;
+        if (reinterpret_cast<uintptr_t>(in.ptr) % 4) {   // a view at an odd offset: the kernels read 4-byte pairs
+            in.keep = t.attr("clone")();
+            in.ptr = tptr(in.keep);
+        }
+    } else if (k == Kind::i16) {
+        py::object o = py::reinterpret_borrow<py::object>(x);
+        if (py::isinstance<py::array>(o)) o = py::module_::import("numpy").attr("ascontiguousarray")(o);
+        py::buffer_info bi = py::reinterpret_borrow<py::buffer>(o).request();
+        in.ptr = bi.ptr;
+        in.n = (size_t)bi.size * (size_t)bi.itemsize / 4;
+        in.keep = o;
+    } else if (is_device_tensor(x)) {
+        py::object t = dev_cast(x, k).attr("reshape")(-1).attr("contiguous")();
+        on_device(in, t, DevCheck::full);
+        in.n = t.attr("numel")().cast<size_t>();
+    } else {
+        py::array a = host_in(x, k);
+        in.ptr = a.data();
+        in.n = (size_t)a.size();
+        in.keep = std::move(a);
+    }
+    return in;
+}
+
+// The next input of execute_many / filter_resample_many: a device tensor as
+// long as the first and on its device
+void many_in(std::vector<CallIn>& ins, const py::handle& x, Kind k, const std::string& name)
+{
+    if (!is_device_tensor(x)) throw py::value_error(name + ": device tensors only");
+    ins.push_back(in_1d(x, k));
+    if (ins.back().n != ins[0].n) throw py::value_error(name + ": every input must have the same length");
+    if (!ins.back().device.equal(ins[0].device)) throw py::value_error(name + ": every input must be on the same device");
+}
+
+// A [rows, K] input of the class `name`; 1-D stands for one row where `vec`
+// says so.  A device tensor whose columns are one sample apart and whose rows
+// do not overlap is read in place; any other is refused or copied.
+enum class Strided { refuse, copy };
+CallIn in_rows(const py::handle& x, Kind k, unsigned rows, const std::string& name, bool vec, Strided policy)
+{
+    auto check_rows = [&](py::ssize_t ndim, py::ssize_t got) {
+        if (ndim != 2)
+            throw py::value_error(name + ": the input must be 2-D, [nchan, K]" + (vec ? " (1-D when nchan is 1)" : ""));
+        if (got != (py::ssize_t)rows)
+            throw py::value_error(name + ": the input has " + std::to_string(got) + " rows, nchan is " +
+                                  std::to_string(rows));
+    };
+    CallIn in;
+    if (!is_device_tensor(x)) {
+        py::array a = host_in(x, k);
+        if (vec && rows == 1 && a.ndim() == 1) a = a.reshape({(py::ssize_t)1, a.shape(0)});
+        check_rows(a.ndim(), a.ndim() == 2 ? a.shape(0) : 0);
+        in.ptr = a.data();
+        in.n = in.ld = (size_t)a.shape(1);
+        in.keep = std::move(a);
         return in;
     }
-    py::object o = py::reinterpret_borrow<py::object>(b);
-    if (py::isinstance<py::array>(o)) o = py::module_::import("numpy").attr("ascontiguousarray")(o);
-    py::buffer_info bi = py::reinterpret_borrow<py::buffer>(o).request();
-    in.ptr = bi.ptr;
-    in.n = (size_t)bi.size * (size_t)bi.itemsize / 4;
-    in.keep = o;
+    py::object t = py::reinterpret_borrow<py::object>(x);
+    int dim = t.attr("dim")().cast<int>();
+    if (vec && rows == 1 && dim == 1) {
+        t = t.attr("unsqueeze")(0);
+        dim = 2;
+    }
+    check_rows(dim, dim == 2 ? t.attr("size")(0).cast<py::ssize_t>() : 0);
+    t = dev_cast(t, k);
+    const size_t K = t.attr("size")(1).cast<size_t>();
+    long s0 = t.attr("stride")(0).cast<long>();
+    const bool apart = t.attr("stride")(1).cast<long>() != 1, overlap = s0 < (long)K;
+    if (policy == Strided::refuse) {
+        if (K > 1 && apart)
+            throw py::value_error(name + ": the input's columns must be one sample apart (stride(1) == 1)");
+        if (rows > 1 && overlap)
+            throw py::value_error(name + ": the input's row stride must be at least its number of columns");
+        in.ld = rows > 1 ? (size_t)s0 : K;
+    } else {
+        if (apart || overlap) {
+            t = t.attr("contiguous")();
+            s0 = t.attr("stride")(0).cast<long>();
+        }
+        in.ld = std::max<size_t>((size_t)s0, K);
+    }
+    in.n = K;
+    on_device(in, t, DevCheck::full);
     return in;
 }
 
@@ -158,79 +271,121 @@ CallIn raw_in(const py::handle& b)
 // the call DMAs into them and a following call DMAs out of them without a staging
 // copy (the README chain hands each stage's array to the next); ordinary
 // writeable numpy arrays otherwise alike.  Pageable when the pool is exhausted.
-template <typename T>
-py::array host_array(size_t n)
+using Shape = std::vector<py::ssize_t>;
+py::array host_array(Kind k, size_t n)
 {
+    const size_t bytes = n * kind_size(k);
     void* p = nullptr;
-    if (n * sizeof(T) >= ((size_t)64 << 10) && ldsp_host_alloc(n * sizeof(T), &p) == LDSP_OK) {
+    if (bytes >= ((size_t)64 << 10) && ldsp_host_alloc(bytes, &p) == LDSP_OK) {
         py::capsule owner(p, [](void* q) { ldsp_host_free(q); });
-        return py::array_t<T>({(py::ssize_t)n}, {(py::ssize_t)sizeof(T)}, static_cast<T*>(p), owner);
+        return py::array(np_dtype(k), Shape{(py::ssize_t)n}, Shape{(py::ssize_t)kind_size(k)}, p, owner);
     }
-    return py::array_t<T>(n);
+    return py::array(np_dtype(k), Shape{(py::ssize_t)n});
 }
-py::array host_array(size_t n, bool cplx) { return cplx ? host_array<cf>(n) : host_array<float>(n); }
 
-using carr = py::array_t<cf, py::array::c_style | py::array::forcecast>;
-using farr = py::array_t<float, py::array::c_style | py::array::forcecast>;
-
-// complex64 input of the same objects' __call__: a device tensor as it is, anything else force-cast
-CallIn cplx_in(const py::handle& x)
+// A call's result where its input is: a device tensor on the input's device or
+// a numpy array (1-D: host_array; 2-D: an ordinary array), n or [n, cols] of kind k.
+struct CallOut {
+    py::object obj;
+    void* ptr = nullptr;
+};
+CallOut make_out(const CallIn& in, Kind k, size_t n, py::ssize_t cols = -1)
 {
-    CallIn in;
-    if (is_device_tensor(x)) {
-        DevIn d = dev_in(x, true);
-        in.keep = d.t;
-        in.ptr = d.ptr;
-        in.n = d.n;
-        in.dev = true;
-        in.stream = d.stream;
-        in.device = d.device;
-        return in;
+    CallOut o;
+    if (in.dev) {
+        py::object& torch = torch_mod();
+        py::dict kw;
+        kw["dtype"] = torch.attr(torch_name(k));
+        kw["device"] = in.device;
+        o.obj = cols < 0 ? torch.attr("empty")(py::int_(n), **kw) : torch.attr("empty")(py::make_tuple(n, cols), **kw);
+        o.ptr = tptr(o.obj);
+        return o;
     }
-    carr a = carr::ensure(x);
-    if (!a) throw py::error_already_set();
-    in.ptr = a.data();
-    in.n = (size_t)a.size();
-    in.keep = std::move(a);
-    return in;
+    py::array a = cols < 0 ? host_array(k, n) : py::array(np_dtype(k), Shape{(py::ssize_t)n, cols});
+    o.ptr = a.mutable_data();
+    o.obj = std::move(a);
+    return o;
+}
+
+// f(mem, stream) -> rc where the input is: on the device on its stream, the GIL
+// held; on the host with the GIL released while the call waits for the GPU.
+template <typename F>
+void invoke(const CallIn& in, F&& f)
+{
+    int rc;
+    if (in.dev) {
+        rc = f(LDSP_MEM_DEVICE, in.stream);
+    } else {
+        py::gil_scoped_release rel;
+        rc = f(LDSP_MEM_HOST, (void*)nullptr);
+    }
+    check(rc);
 }
 
 // Same-length stage (FIR / IIR / NCO / AGC): in -> out of the given kinds
 template <typename F>
-py::object run_same(const py::handle& x, bool cin, bool cout, F&& exec)
+py::object run_same(const py::handle& x, Kind kin, Kind kout, F&& exec)
 {
-    if (is_device_tensor(x)) {
-        DevIn d = dev_in(x, cin);
-        py::object out = dev_empty(d.n, cout, d.device);
-        check(exec(d.ptr, d.n, tptr(out), LDSP_MEM_DEVICE, d.stream));
-        return out;
-    }
-    if (cin) {
-        carr a = carr::ensure(x);
-        if (!a) throw py::error_already_set();
-        const size_t n = (size_t)a.size();
-        py::object out = host_array(n, cout);
-        void* yp = py::array(out).mutable_data();
-        int rc;
-        {
-            py::gil_scoped_release rel;
-            rc = exec((const void*)a.data(), n, yp, LDSP_MEM_HOST, nullptr);
-        }
-        check(rc);
-        return out;
-    }
-    farr a = farr::ensure(x);
-    if (!a) throw py::error_already_set();
-    const size_t n = (size_t)a.size();
-    py::object out = host_array(n, cout);
-    void* yp = py::array(out).mutable_data();
-    int rc;
-    {
-        py::gil_scoped_release rel;
-        rc = exec((const void*)a.data(), n, yp, LDSP_MEM_HOST, nullptr);
-    }
-    check(rc);
-    return out;
+    const CallIn in = in_1d(x, kin);
+    CallOut out = make_out(in, kout, in.n);
+    invoke(in, [&](int mem, void* s) { return exec(in.ptr, in.n, out.ptr, mem, s); });
+    return out.obj;
+}
+
+// 1-D in, num_outputs(n) out (the resamplers, FMStereo, filter_resample)
+template <typename N, typename F>
+py::object run_counted(const py::handle& x, Kind kin, Kind kout, N&& num_outputs, F&& exec)
+{
+    const CallIn in = in_1d(x, kin);
+    size_t nout = 0, nw = 0;
+    check(num_outputs(in.n, &nout));
+    CallOut out = make_out(in, kout, nout);
+    invoke(in, [&](int mem, void* s) { return exec(in.ptr, in.n, out.ptr, nout, &nw, mem, s); });
+    return out.obj;
+}
+
+// 1-D in (complex64, or int16 IQ pairs converted by the kernel's loads: exec16),
+// complex64[rows, num_outputs(n)] out (Channelizer, Downconverter)
+template <typename Q, typename E>
+py::object run_to_rows(Q q, const py::handle& x, bool iq16, unsigned rows, int (*num_outputs)(Q, size_t, size_t*),
+                       E exec, E exec16)
+{
+    const CallIn in = in_1d(x, iq16 ? Kind::i16 : Kind::c64);
+    size_t K = 0, nw = 0;
+    check(num_outputs(q, in.n, &K));
+    CallOut out = make_out(in, Kind::c64, rows, (py::ssize_t)K);
+    invoke(in, [&](int mem, void* s) { return (iq16 ? exec16 : exec)(q, in.ptr, in.n, out.ptr, K, &nw, mem, s); });
+    return out.obj;
+}
+
+// A row image in (in_rows), num_outputs(K) per row out: kout[orows, N], or
+// kout[N] where orows < 0 (FMBank, AudioBank, Synthesizer)
+template <typename Q>
+py::object run_from_rows(Q q, const CallIn& in, Kind kout, py::ssize_t orows, int (*num_outputs)(Q, size_t, size_t*),
+                         int (*exec)(Q, const void*, size_t, size_t, void*, size_t, size_t*, int, void*))
+{
+    size_t N = 0, nw = 0;
+    check(num_outputs(q, in.n, &N));
+    CallOut out = orows < 0 ? make_out(in, kout, N) : make_out(in, kout, (size_t)orows, (py::ssize_t)N);
+    invoke(in, [&](int mem, void* s) { return exec(q, in.ptr, in.ld, in.n, out.ptr, N, &nw, mem, s); });
+    return out.obj;
+}
+
+// The optional Fc of the banks: None stands for the C ABI's default (0)
+float opt_cutoff(const py::object& fc, const std::string& name)
+{
+    if (fc.is_none()) return 0.0f;
+    const float f = fc.cast<float>();
+    if (!(f > 0.0f && f < 0.5f)) throw py::value_error(name + ": Fc must lie in (0, 0.5)");
+    return f;
+}
+
+// k / N wrapped into [-0.5, 0.5)
+py::array_t<double> wrapped_centers(unsigned N)
+{
+    py::array_t<double> c(N);
+    for (unsigned k = 0; k < N; k++) c.mutable_at(k) = std::fmod((double)k / N + 0.5, 1.0) - 0.5;
+    return c;
 }
 
 std::vector<float> to_fvec(const py::handle& h)
@@ -242,11 +397,8 @@ std::vector<float> to_fvec(const py::handle& h)
 
 // ------------------------------------------------------------------ FIR
 struct FIR {
-    ldsp_firfilt_t q = nullptr;
+    Handle<ldsp_firfilt_t, ldsp_firfilt_destroy> q;
     bool cplx = false;
-    FIR() = default;
-    FIR(const FIR&) = delete;
-    ~FIR() { if (q) ldsp_firfilt_destroy(q); }
     cf freqresponse(float f)
     {
         float re, im;
@@ -255,15 +407,12 @@ struct FIR {
     }
     py::object call(const py::handle& x)
     {
-        return run_same(x, cplx, cplx, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
+        return run_same(x, kind_of(cplx), kind_of(cplx), [&](const void* xi, size_t n, void* yo, int mem, void* s) {
             return ldsp_firfilt_execute(q, xi, n, yo, mem, s);
         });
     }
     void reset() { check(ldsp_firfilt_reset(q)); }
-    bool get_exact()
-    {
-        return exact_;
-    }
+    bool get_exact() { return exact_; }
     void set_exact(bool e)
     {
         check(ldsp_firfilt_set_mode(q, e ? LDSP_MODE_EXACT : LDSP_MODE_FAST));
@@ -295,12 +444,7 @@ struct FIR {
         check(ldsp_firfilt_get_taps(q, h.mutable_data()));
         return h;
     }
-    float get_scale()
-    {
-        float s;
-        check(ldsp_firfilt_get_scale(q, &s));
-        return s;
-    }
+    float get_scale() { return get_value<float>(ldsp_firfilt_get_scale, q); }
     bool exact_ = false;
 };
 
@@ -310,7 +454,7 @@ struct RealFIRFilter : FIR {
     explicit RealFIRFilter(const py::handle& h)
     {
         std::vector<float> v = to_fvec(h);
-        check(ldsp_firfilt_create(v.data(), (unsigned)v.size(), 0, &q));
+        check(ldsp_firfilt_create(v.data(), (unsigned)v.size(), 0, q.out()));
     }
 };
 // ComplexFIRFilter: new class (firfilt_crcf semantics of demod.hpp:105,135-136)
@@ -319,7 +463,7 @@ struct ComplexFIRFilter : FIR {
     {
         cplx = true;
         std::vector<float> v = to_fvec(h);
-        check(ldsp_firfilt_create(v.data(), (unsigned)v.size(), 1, &q));
+        check(ldsp_firfilt_create(v.data(), (unsigned)v.size(), 1, q.out()));
     }
 };
 // RealDCBlocker (firfilter.hpp:38-50)
@@ -327,7 +471,7 @@ struct RealDCBlocker : FIR {
     RealDCBlocker(int m, float as)
     {
         if (m < 1) throw py::value_error("RealDCBlocker: slen must be >= 1");
-        check(ldsp_firfilt_create_dc_blocker((unsigned)m, as, 0, &q));
+        check(ldsp_firfilt_create_dc_blocker((unsigned)m, as, 0, q.out()));
     }
 };
 // RealKaiserBessel (firfilter.hpp:52-66): unit DC gain via set_scale(1/|H(0)|)
@@ -335,7 +479,7 @@ struct RealKaiserBessel : FIR {
     RealKaiserBessel(int flen, float fc, float as, float offset)
     {
         if (flen < 1) throw py::value_error("RealKaiserBessel: flen must be >= 1");
-        check(ldsp_firfilt_create_kaiser((unsigned)flen, fc, as, offset, 0, &q));
+        check(ldsp_firfilt_create_kaiser((unsigned)flen, fc, as, offset, 0, q.out()));
         const cf res0 = freqresponse(0.0f);
         check(ldsp_firfilt_set_scale(q, (float)(1.0 / (double)std::abs(res0))));
     }
@@ -343,7 +487,7 @@ struct RealKaiserBessel : FIR {
 
 // ------------------------------------------------------------------ resamplers
 struct Resampler {
-    ldsp_resamp_t q = nullptr;
+    Handle<ldsp_resamp_t, ldsp_resamp_destroy> q;
     bool cplx;
     float rate_, fc_, as_;
     int m_, npfb_;
@@ -351,15 +495,13 @@ struct Resampler {
     {
         if (d < 1) throw py::value_error("resampler: len must be >= 1");
         if (nf < 1) throw py::value_error("resampler: nfilter must be >= 1");
-        check(ldsp_resamp_create(r, (unsigned)d, fc, sbsp, (unsigned)nf, c ? 1 : 0, &q));
+        check(ldsp_resamp_create(r, (unsigned)d, fc, sbsp, (unsigned)nf, c ? 1 : 0, q.out()));
     }
     // resamp_*_create_default(rate) (RResampler / CResampler, resampler.hpp:10-13,46-49); kind 0 rrrf, 2 crcf
     Resampler(float r, int kind) : cplx(kind != 0), rate_(r), fc_(0.25f), as_(60.0f), m_(7), npfb_(256)
     {
-        check(ldsp_resamp_create_default(r, kind, &q));
+        check(ldsp_resamp_create_default(r, kind, q.out()));
     }
-    Resampler(const Resampler&) = delete;
-    ~Resampler() { if (q) ldsp_resamp_destroy(q); }
     void reset() { check(ldsp_resamp_reset(q)); }
     float get_rate() { return rate_; }
     void set_rate(float r)
@@ -375,33 +517,16 @@ struct Resampler {
         py::print(py::str("<liquid.resamp_{}, rate={}, m={}, as={:.3f}, fc={:.3f}, npfb={}>")
                       .format(cplx ? "cccf" : "rrrf", rate_, m_, as_, fc_, npfb));
     }
-    py::object call(const py::handle& x)
+    py::object call(const py::handle& x) { return run(x, nullptr); }
+    // self(x); with a filter, self(iir(x)) in one pass (filter_resample)
+    py::object run(const py::handle& x, ldsp_iirfilt_t iir)
     {
-        if (is_device_tensor(x)) {
-            DevIn d = dev_in(x, cplx);
-            size_t nout = 0;
-            check(ldsp_resamp_num_outputs(q, d.n, &nout));
-            py::object out = dev_empty(nout, cplx, d.device);
-            size_t nw = 0;
-            check(ldsp_resamp_execute(q, d.ptr, d.n, tptr(out), nout, &nw, LDSP_MEM_DEVICE, d.stream));
-            return out;
-        }
-        py::array a = cplx ? py::array(carr::ensure(x)) : py::array(farr::ensure(x));
-        if (!a) throw py::error_already_set();
-        const size_t n = (size_t)a.size();
-        size_t nout = 0;
-        check(ldsp_resamp_num_outputs(q, n, &nout));
-        py::array out = host_array(nout, cplx);
-        void* yp = out.mutable_data();
-        const void* xp = a.data();
-        size_t nw = 0;
-        int rc;
-        {
-            py::gil_scoped_release rel;
-            rc = ldsp_resamp_execute(q, xp, n, yp, nout, &nw, LDSP_MEM_HOST, nullptr);
-        }
-        check(rc);
-        return out;
+        return run_counted(
+            x, kind_of(cplx), kind_of(cplx), [&](size_t n, size_t* k) { return ldsp_resamp_num_outputs(q, n, k); },
+            [&](const void* xi, size_t n, void* yo, size_t cap, size_t* nw, int mem, void* s) {
+                return iir ? ldsp_iirfilt_resamp_execute(iir, q, xi, n, yo, cap, nw, mem, s)
+                           : ldsp_resamp_execute(q, xi, n, yo, cap, nw, mem, s);
+            });
     }
 };
 
@@ -417,12 +542,9 @@ int ftype_of(const std::string& s)
 }
 
 struct IIR {
-    ldsp_iirfilt_t q = nullptr;
+    Handle<ldsp_iirfilt_t, ldsp_iirfilt_destroy> q;
     bool cplx = true;
     bool exact_ = false;
-    IIR() = default;
-    IIR(const IIR&) = delete;
-    ~IIR() { if (q) ldsp_iirfilt_destroy(q); }
     void reset() { check(ldsp_iirfilt_reset(q)); }
     cf freqresponse(float f)
     {
@@ -432,7 +554,7 @@ struct IIR {
     }
     py::object call(const py::handle& x)
     {
-        return run_same(x, cplx, cplx, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
+        return run_same(x, kind_of(cplx), kind_of(cplx), [&](const void* xi, size_t n, void* yo, int mem, void* s) {
             return ldsp_iirfilt_execute(q, xi, n, yo, mem, s);
         });
     }
@@ -443,21 +565,9 @@ struct IIR {
     py::object from_bytes(const py::handle& b)
     {
         if (!cplx) throw py::value_error("from_bytes: int16 IQ input needs a complex filter");
-        const CallIn in = raw_in(b);
-        if (in.dev) {
-            py::object out = dev_empty(in.n, true, in.device);
-            check(ldsp_iirfilt_execute_iq16(q, in.ptr, in.n, tptr(out), LDSP_MEM_DEVICE, in.stream));
-            return out;
-        }
-        py::array_t<cf> out = host_array<cf>(in.n);
-        void* yp = out.mutable_data();
-        int rc;
-        {
-            py::gil_scoped_release rel;
-            rc = ldsp_iirfilt_execute_iq16(q, in.ptr, in.n, yp, LDSP_MEM_HOST, nullptr);
-        }
-        check(rc);
-        return std::move(out);
+        return run_same(b, Kind::i16, Kind::c64, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
+            return ldsp_iirfilt_execute_iq16(q, xi, n, yo, mem, s);
+        });
     }
     bool get_exact() { return exact_; }
     void set_exact(bool e)
@@ -496,7 +606,7 @@ struct TFIIR : IIR {
     {
         cplx = c;
         std::vector<float> b = to_fvec(bc), a = to_fvec(ac);
-        check(ldsp_iirfilt_create_tf(b.data(), (unsigned)b.size(), a.data(), (unsigned)a.size(), c ? 1 : 0, &q));
+        check(ldsp_iirfilt_create_tf(b.data(), (unsigned)b.size(), a.data(), (unsigned)a.size(), c ? 1 : 0, q.out()));
     }
 };
 
@@ -506,7 +616,7 @@ struct BandIIR : IIR {
     {
         cplx = c;
         if (order < 1) throw py::value_error("iirfilt: order must be >= 1");
-        check(ldsp_iirfilt_create_prototype(ftype_of(typ), btype, (unsigned)order, fc, f0, ap, as, c ? 1 : 0, &q));
+        check(ldsp_iirfilt_create_prototype(ftype_of(typ), btype, (unsigned)order, fc, f0, ap, as, c ? 1 : 0, q.out()));
     }
 };
 
@@ -531,7 +641,7 @@ struct ProtoIIR : IIR {
             bti = bi->second;
         }
         if (order < 1) throw py::value_error("iirfilt: order must be >= 1");
-        check(ldsp_iirfilt_create_prototype(fti, bti, (unsigned)order, fc, f0, ap, as, c ? 1 : 0, &q));
+        check(ldsp_iirfilt_create_prototype(fti, bti, (unsigned)order, fc, f0, ap, as, c ? 1 : 0, q.out()));
     }
 };
 
@@ -545,35 +655,23 @@ struct DeemphasisFilter : IIR {
         mA[0] = 1.0f;
         mA[1] = -x;
         mB[0] = (float)(1.0 - (double)x);
-        check(ldsp_iirfilt_create_tf(mB, 1, mA, 2, 0, &q));
+        check(ldsp_iirfilt_create_tf(mB, 1, mA, 2, 0, q.out()));
     }
 };
 
 // ------------------------------------------------------------------ NCO (nco.hpp:4-81)
 struct NCO {
-    ldsp_nco_t q = nullptr;
+    Handle<ldsp_nco_t, ldsp_nco_destroy> q;
     std::string mType;
     explicit NCO(const std::string& type)
     {
         mType = (type == "nco") ? "nco" : "vco";
-        check(ldsp_nco_create(type == "nco" ? 0 : 1, &q));
+        check(ldsp_nco_create(type == "nco" ? 0 : 1, q.out()));
     }
-    NCO(const NCO&) = delete;
-    ~NCO() { if (q) ldsp_nco_destroy(q); }
-    float frequency()
-    {
-        float f;
-        check(ldsp_nco_get_frequency(q, &f));
-        return f;
-    }
+    float frequency() { return get_value<float>(ldsp_nco_get_frequency, q); }
     void set_frequency(float f) { check(ldsp_nco_set_frequency(q, f)); }
     void adjust_frequency(float df) { check(ldsp_nco_adjust_frequency(q, df)); }
-    float phase()
-    {
-        float p;
-        check(ldsp_nco_get_phase(q, &p));
-        return p;
-    }
+    float phase() { return get_value<float>(ldsp_nco_get_phase, q); }
     void set_phase(float p) { check(ldsp_nco_set_phase(q, p)); }
     void adjust_phase(float dp) { check(ldsp_nco_adjust_phase(q, dp)); }
     void set_pll_bandwidth(float bw) { check(ldsp_nco_pll_set_bandwidth(q, bw)); }
@@ -590,7 +688,7 @@ struct NCO {
     }
     py::object mix(const py::handle& x, bool down)
     {
-        return run_same(x, true, true, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
+        return run_same(x, Kind::c64, Kind::c64, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
             return ldsp_nco_mix(q, xi, n, yo, down ? 1 : 0, mem, s);
         });
     }
@@ -601,19 +699,12 @@ struct NCO {
 int g_state_last = 0;   // LIQUID_AGC_SQUELCH_UNKNOWN
 
 struct AGC {
-    ldsp_agc_t q = nullptr;
+    Handle<ldsp_agc_t, ldsp_agc_destroy> q;
     bool mSquelch = false, mLock = false;
     py::object mOnRise = py::none();
-    AGC() { check(ldsp_agc_create(&q)); }
-    AGC(const AGC&) = delete;
-    ~AGC() { if (q) ldsp_agc_destroy(q); }
+    AGC() { check(ldsp_agc_create(q.out())); }
     template <typename T, typename G>
-    T get(G g)
-    {
-        T v;
-        check(g(q, &v));
-        return v;
-    }
+    T get(G g) { return get_value<T>(g, q); }
     void set_bandwidth(float bw) { check(ldsp_agc_set_bandwidth(q, bw)); }
     float get_bandwidth() { return get<float>(ldsp_agc_get_bandwidth); }
     bool get_squelch() { return mSquelch; }
@@ -652,7 +743,7 @@ struct AGC {
         // (otherwise every status is LIQUID_AGC_SQUELCH_DISABLED).
         std::vector<uint8_t> st;
         const bool need = mSquelch;
-        py::object out = run_same(x, true, true, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
+        py::object out = run_same(x, Kind::c64, Kind::c64, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
             if (need) st.resize(n);
             return ldsp_agc_execute(q, xi, n, yo, need ? st.data() : nullptr, mem, s);
         });
@@ -680,27 +771,19 @@ struct AmpModem {
     float mModulation;
     std::string mType;
     bool mCarrier;
-    ldsp_ampmodem_t q = nullptr;
+    Handle<ldsp_ampmodem_t, ldsp_ampmodem_destroy> q;
     AmpModem(float mod, const std::string& type, bool car) : mModulation(mod), mCarrier(car) { make(mod, type, car); }
-    AmpModem(const AmpModem&) = delete;
-    ~AmpModem() { destroy(); }
-    void destroy()
-    {
-        if (q) ldsp_ampmodem_destroy(q);
-        q = nullptr;
-    }
     // makeFromArgs (demod.hpp:298-306): a known type string is recorded, an
     // unknown one leaves mType unchanged and demodulates DSB.
     void make(float mod, const std::string& type, bool car)
     {
-        ldsp_ampmodem_t nq = nullptr;
+        Handle<ldsp_ampmodem_t, ldsp_ampmodem_destroy> nq;
         int mt = 0;
         auto it = kAmpTypes.find(type);
         if (it != kAmpTypes.end()) mt = it->second;
-        check(ldsp_ampmodem_create(mod, mt, car ? 0 : 1, &nq));
+        check(ldsp_ampmodem_create(mod, mt, car ? 0 : 1, nq.out()));
         if (it != kAmpTypes.end()) mType = type;
-        destroy();
-        q = nq;
+        q = std::move(nq);      // the old modem goes with nq
     }
     // The setters rebuild the modem (state reset, demod.hpp:250-276).  The new
     // handle is created first and swapped in only on success, so a setter that
@@ -766,7 +849,7 @@ struct AmpModem {
     }
     py::object demod(const py::handle& x)
     {
-        return run_same(x, true, false, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
+        return run_same(x, Kind::c64, Kind::f32, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
             return ldsp_ampmodem_demodulate(q, xi, n, yo, mem, s);
         });
     }
@@ -775,28 +858,18 @@ struct AmpModem {
 
 // ------------------------------------------------------------------ BroadcastAM (demod.hpp:93-153)
 struct BroadcastAM {
-    ldsp_bcastam_t q = nullptr;
+    Handle<ldsp_bcastam_t, ldsp_bcastam_destroy> q;
     explicit BroadcastAM(int m)
     {
         if (m < 1) throw py::value_error("BroadcastAM: slen must be >= 1");
-        check(ldsp_bcastam_create((unsigned)m, &q));
-    }
-    BroadcastAM(const BroadcastAM&) = delete;
-    ~BroadcastAM()
-    {
-        if (q) ldsp_bcastam_destroy(q);
+        check(ldsp_bcastam_create((unsigned)m, q.out()));
     }
     void reset() { check(ldsp_bcastam_reset(q)); }
-    bool get_exact()
-    {
-        int m = 0;
-        check(ldsp_bcastam_get_mode(q, &m));
-        return m == LDSP_MODE_EXACT;
-    }
+    bool get_exact() { return get_value<int>(ldsp_bcastam_get_mode, q) == LDSP_MODE_EXACT; }
     void set_exact(bool e) { check(ldsp_bcastam_set_mode(q, e ? LDSP_MODE_EXACT : LDSP_MODE_FAST)); }
     py::object call(const py::handle& x)
     {
-        return run_same(x, true, false, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
+        return run_same(x, Kind::c64, Kind::f32, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
             return ldsp_bcastam_demodulate(q, xi, n, yo, nullptr, mem, s);
         });
     }
@@ -804,19 +877,14 @@ struct BroadcastAM {
 
 // ------------------------------------------------------------------ FreqDem (demod.hpp:189-219)
 struct FreqDem {
-    ldsp_freqdem_t q = nullptr;
+    Handle<ldsp_freqdem_t, ldsp_freqdem_destroy> q;
     float kf;
-    explicit FreqDem(float k) : kf(k) { check(ldsp_freqdem_create(k, &q)); }
-    FreqDem(const FreqDem&) = delete;
-    ~FreqDem()
-    {
-        if (q) ldsp_freqdem_destroy(q);
-    }
+    explicit FreqDem(float k) : kf(k) { check(ldsp_freqdem_create(k, q.out())); }
     void reset() { check(ldsp_freqdem_reset(q)); }
     void print() { py::print(py::str("freqdem:\n    mod. factor :  {:8.4f}").format(kf)); }
     py::object call(const py::handle& x)
     {
-        return run_same(x, true, false, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
+        return run_same(x, Kind::c64, Kind::f32, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
             return ldsp_freqdem_demodulate(q, xi, n, yo, mem, s);
         });
     }
@@ -824,13 +892,8 @@ struct FreqDem {
 
 // ------------------------------------------------------------------ FMStereo (demod.hpp:4-85)
 struct FMStereo {
-    ldsp_fmstereo_t q = nullptr;
-    FMStereo(float iq_rate, float pcm_rate) { check(ldsp_fmstereo_create(iq_rate, pcm_rate, &q)); }
-    FMStereo(const FMStereo&) = delete;
-    ~FMStereo()
-    {
-        if (q) ldsp_fmstereo_destroy(q);
-    }
+    Handle<ldsp_fmstereo_t, ldsp_fmstereo_destroy> q;
+    FMStereo(float iq_rate, float pcm_rate) { check(ldsp_fmstereo_create(iq_rate, pcm_rate, q.out())); }
     void reset() { check(ldsp_fmstereo_reset(q)); }
     py::tuple state()
     {
@@ -842,53 +905,23 @@ struct FMStereo {
     // complex64 IQ -> interleaved (L, R) float32
     py::object call(const py::handle& x)
     {
-        if (is_device_tensor(x)) {
-            DevIn d = dev_in(x, true);
-            size_t nout = 0;
-            check(ldsp_fmstereo_num_outputs(q, d.n, &nout));
-            py::object out = dev_empty(nout, false, d.device);
-            size_t nw = 0;
-            check(ldsp_fmstereo_execute(q, d.ptr, d.n, tptr(out), nout, &nw, LDSP_MEM_DEVICE, d.stream));
-            return out;
-        }
-        carr a = carr::ensure(x);
-        if (!a) throw py::error_already_set();
-        const size_t n = (size_t)a.size();
-        size_t nout = 0;
-        check(ldsp_fmstereo_num_outputs(q, n, &nout));
-        py::array_t<float> out = host_array<float>(nout);
-        void* yp = out.mutable_data();
-        const void* xp = a.data();
-        size_t nw = 0;
-        int rc;
-        {
-            py::gil_scoped_release rel;
-            rc = ldsp_fmstereo_execute(q, xp, n, yp, nout, &nw, LDSP_MEM_HOST, nullptr);
-        }
-        check(rc);
-        return std::move(out);
+        return run_counted(
+            x, Kind::c64, Kind::f32, [&](size_t n, size_t* k) { return ldsp_fmstereo_num_outputs(q, n, k); },
+            [&](const void* xi, size_t n, void* yo, size_t cap, size_t* nw, int mem, void* s) {
+                return ldsp_fmstereo_execute(q, xi, n, yo, cap, nw, mem, s);
+            });
     }
 };
 
 // ------------------------------------------------------------------ Delay (utility.hpp:5-57)
 struct Delay {
-    ldsp_delay_t q = nullptr;
+    Handle<ldsp_delay_t, ldsp_delay_destroy> q;
     explicit Delay(int nd)
     {
         if (nd < 0) throw py::value_error("Delay: nd must be >= 0");
-        check(ldsp_delay_create((unsigned)nd, &q));
+        check(ldsp_delay_create((unsigned)nd, q.out()));
     }
-    Delay(const Delay&) = delete;
-    ~Delay()
-    {
-        if (q) ldsp_delay_destroy(q);
-    }
-    int get_delay()
-    {
-        unsigned nd = 0;
-        check(ldsp_delay_get_delay(q, &nd));
-        return (int)nd;
-    }
+    int get_delay() { return (int)get_value<unsigned>(ldsp_delay_get_delay, q); }
     void set_delay(int nd)
     {
         if (nd < 0) throw py::value_error("Delay: nd must be >= 0");
@@ -897,69 +930,34 @@ struct Delay {
     // dispatch on dtype like the reference: complex64 / float32, anything else -> None
     py::object call(const py::handle& x)
     {
-        py::object tp = py::getattr(x, "dtype");
-        int kind = -1;
-        if (is_device_tensor(x)) {
-            py::object& torch = torch_mod();
-            if (tp.equal(torch.attr("complex64"))) kind = 1;
-            else if (tp.equal(torch.attr("float32"))) kind = 0;
-        } else {
-            if (tp.equal(py::dtype("complex64"))) kind = 1;
-            else if (tp.equal(py::dtype("float32"))) kind = 0;
-        }
-        if (kind < 0) return py::none();
-        const bool c = kind == 1;
-        return run_same(x, c, c, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
-            return ldsp_delay_execute(q, xi, n, c ? 1 : 0, yo, mem, s);
+        Kind k;
+        if (!kind_from_dtype(x, &k)) return py::none();
+        return run_same(x, k, k, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
+            return ldsp_delay_execute(q, xi, n, k == Kind::c64 ? 1 : 0, yo, mem, s);
         });
     }
 };
 
 // ------------------------------------------------------------------ firhilbf (demod.hpp:155-187, utility.hpp:71-108)
 struct Hilb {
-    ldsp_firhilb_t q = nullptr;
+    Handle<ldsp_firhilb_t, ldsp_firhilb_destroy> q;
     Hilb(int m, float as, int op)
     {
         if (m < 0) throw py::value_error("firhilb: m must be >= 2");
-        check(ldsp_firhilb_create((unsigned)m, as, op, &q));
-    }
-    Hilb(const Hilb&) = delete;
-    ~Hilb()
-    {
-        if (q) ldsp_firhilb_destroy(q);
+        check(ldsp_firhilb_create((unsigned)m, as, op, q.out()));
     }
     // One call: n input samples -> nout(n) outputs per returned array; two arrays
     // (lower, upper) when `both`, else the output goes to y0 (y1 when `second`).
-    py::object run(const py::handle& x, bool cin, bool cout, size_t (*nout)(size_t), bool both = false,
+    py::object run(const py::handle& x, Kind kin, Kind kout, size_t (*nout)(size_t), bool both = false,
                    bool second = false)
     {
-        auto pick = [&](void* a, void* b, void** y0, void** y1) {
-            *y0 = both || !second ? a : nullptr;
-            *y1 = both ? b : (second ? a : nullptr);
-        };
-        void *y0, *y1;
-        if (is_device_tensor(x)) {
-            DevIn d = dev_in(x, cin);
-            py::object o0 = dev_empty(nout(d.n), cout, d.device);
-            py::object o1 = both ? dev_empty(nout(d.n), cout, d.device) : py::none();
-            pick(tptr(o0), both ? tptr(o1) : nullptr, &y0, &y1);
-            check(ldsp_firhilb_execute(q, d.ptr, d.n, y0, y1, LDSP_MEM_DEVICE, d.stream));
-            return both ? py::object(py::make_tuple(o0, o1)) : o0;
-        }
-        py::array a = cin ? py::array(carr::ensure(x)) : py::array(farr::ensure(x));
-        if (!a) throw py::error_already_set();
-        const size_t n = (size_t)a.size();
-        py::array o0 = host_array(nout(n), cout);
-        py::array o1 = both ? host_array(nout(n), cout) : py::array();
-        pick(o0.mutable_data(), both ? o1.mutable_data() : nullptr, &y0, &y1);
-        const void* xp = a.data();
-        int rc;
-        {
-            py::gil_scoped_release rel;
-            rc = ldsp_firhilb_execute(q, xp, n, y0, y1, LDSP_MEM_HOST, nullptr);
-        }
-        check(rc);
-        return both ? py::object(py::make_tuple(o0, o1)) : py::object(o0);
+        const CallIn in = in_1d(x, kin);
+        CallOut o0 = make_out(in, kout, nout(in.n)), o1;
+        if (both) o1 = make_out(in, kout, nout(in.n));
+        void* y0 = both || !second ? o0.ptr : nullptr;
+        void* y1 = both ? o1.ptr : (second ? o0.ptr : nullptr);
+        invoke(in, [&](int mem, void* s) { return ldsp_firhilb_execute(q, in.ptr, in.n, y0, y1, mem, s); });
+        return both ? py::object(py::make_tuple(o0.obj, o1.obj)) : o0.obj;
     }
     static size_t same(size_t n) { return n; }
     static size_t half(size_t n) { return n / 2; }
@@ -972,7 +970,7 @@ struct Hilb {
 // contiguous views, usable as the channel inputs of execute_many /
 // filter_resample_many.
 struct Channelizer {
-    ldsp_chan_t q = nullptr;
+    Handle<ldsp_chan_t, ldsp_chan_destroy> q;
     unsigned M = 0, D = 0, L = 0;
     Channelizer(int nchan, const py::object& decim, int m, const py::object& fc, float as, const py::object& taps)
     {
@@ -981,22 +979,13 @@ struct Channelizer {
         if (d < 0) throw py::value_error("Channelizer: decim must be nchan or nchan // 2");
         if (!taps.is_none()) {
             std::vector<float> h = to_fvec(taps);
-            check(ldsp_chan_create_taps((unsigned)nchan, (unsigned)d, h.data(), (unsigned)h.size(), &q));
+            check(ldsp_chan_create_taps((unsigned)nchan, (unsigned)d, h.data(), (unsigned)h.size(), q.out()));
         } else {
             if (m < 0) throw py::value_error("Channelizer: m must be >= 1");
-            float f = 0.0f;                                   // the C ABI's default: 0.5 / nchan
-            if (!fc.is_none()) {
-                f = fc.cast<float>();
-                if (!(f > 0.0f && f < 0.5f)) throw py::value_error("Channelizer: Fc must lie in (0, 0.5)");
-            }
-            check(ldsp_chan_create((unsigned)nchan, (unsigned)d, (unsigned)m, f, as, &q));
+            const float f = opt_cutoff(fc, "Channelizer");    // the C ABI's default: 0.5 / nchan
+            check(ldsp_chan_create((unsigned)nchan, (unsigned)d, (unsigned)m, f, as, q.out()));
         }
         check(ldsp_chan_get_info(q, &M, &D, &L, nullptr));
-    }
-    Channelizer(const Channelizer&) = delete;
-    ~Channelizer()
-    {
-        if (q) ldsp_chan_destroy(q);
     }
     void reset() { check(ldsp_chan_reset(q)); }
     py::array_t<float> taps()
@@ -1005,12 +994,7 @@ struct Channelizer {
         check(ldsp_chan_get_taps(q, h.mutable_data()));
         return h;
     }
-    float get_scale()
-    {
-        float s;
-        check(ldsp_chan_get_scale(q, &s));
-        return s;
-    }
+    float get_scale() { return get_value<float>(ldsp_chan_get_scale, q); }
     void set_scale(float s) { check(ldsp_chan_set_scale(q, s)); }
     unsigned skip()
     {
@@ -1024,42 +1008,20 @@ struct Channelizer {
         check(ldsp_debug_chan_tile(M, D, &f));
         return f;
     }
-    py::array_t<double> centers()
-    {
-        py::array_t<double> c(M);
-        for (unsigned k = 0; k < M; k++) c.mutable_at(k) = std::fmod((double)k / M + 0.5, 1.0) - 0.5;
-        return c;
-    }
+    py::array_t<double> centers() { return wrapped_centers(M); }
     size_t num_outputs(size_t n)
     {
         size_t c = 0;
         check(ldsp_chan_num_outputs(q, n, &c));
         return c;
     }
-    // iq16: the input is int16 (I, Q) pairs, converted by the kernel's loads (ldsp_chan_execute_iq16)
-    py::object run(const CallIn& in, bool iq16)
+    py::object run(const py::handle& x, bool iq16)
     {
-        const auto exec = iq16 ? ldsp_chan_execute_iq16 : ldsp_chan_execute;
-        size_t nw = 0;
-        const size_t K = num_outputs(in.n);
-        if (in.dev) {
-            py::object out = dev_empty2(M, K, true, in.device);
-            check(exec(q, in.ptr, in.n, tptr(out), K, &nw, LDSP_MEM_DEVICE, in.stream));
-            return out;
-        }
-        py::array_t<cf> out({(py::ssize_t)M, (py::ssize_t)K});
-        void* yp = out.mutable_data();
-        int rc;
-        {
-            py::gil_scoped_release rel;
-            rc = exec(q, in.ptr, in.n, yp, K, &nw, LDSP_MEM_HOST, nullptr);
-        }
-        check(rc);
-        return std::move(out);
+        return run_to_rows(q.get(), x, iq16, M, ldsp_chan_num_outputs, ldsp_chan_execute, ldsp_chan_execute_iq16);
     }
-    py::object call(const py::handle& x) { return run(cplx_in(x), false); }
+    py::object call(const py::handle& x) { return run(x, false); }
     // self(bytes_to_iq(raw)) without the complex64 copy: raw as ComplexIIRFilter.from_bytes takes it
-    py::object from_bytes(const py::handle& b) { return run(raw_in(b), true); }
+    py::object from_bytes(const py::handle& b) { return run(b, true); }
 };
 
 // ------------------------------------------------------------------ Downconverter (liquid: nco_crcf + firdecim_crcf)
@@ -1067,7 +1029,7 @@ struct Channelizer {
 // row c the stream mixed down by freqs[c], low-passed and decimated.  The rows
 // of a device result are contiguous views, as the Channelizer's.
 struct Downconverter {
-    ldsp_ddc_t q = nullptr;
+    Handle<ldsp_ddc_t, ldsp_ddc_destroy> q;
     unsigned D = 0, L = 0;
     static std::vector<double> to_freqs(const py::object& f)
     {
@@ -1080,22 +1042,13 @@ struct Downconverter {
         const std::vector<double> f = to_freqs(freqs);
         if (!taps.is_none()) {
             std::vector<float> h = to_fvec(taps);
-            check(ldsp_ddc_create_taps(f.data(), (unsigned)f.size(), (unsigned)decim, h.data(), (unsigned)h.size(), &q));
+            check(ldsp_ddc_create_taps(f.data(), (unsigned)f.size(), (unsigned)decim, h.data(), (unsigned)h.size(), q.out()));
         } else {
             if (m < 0) throw py::value_error("Downconverter: m must be >= 1");
-            float c = 0.0f;                                   // the C ABI's default: 0.5 / decim
-            if (!fc.is_none()) {
-                c = fc.cast<float>();
-                if (!(c > 0.0f && c < 0.5f)) throw py::value_error("Downconverter: Fc must lie in (0, 0.5)");
-            }
-            check(ldsp_ddc_create(f.data(), (unsigned)f.size(), (unsigned)decim, (unsigned)m, c, as, &q));
+            const float c = opt_cutoff(fc, "Downconverter");  // the C ABI's default: 0.5 / decim
+            check(ldsp_ddc_create(f.data(), (unsigned)f.size(), (unsigned)decim, (unsigned)m, c, as, q.out()));
         }
         check(ldsp_ddc_get_info(q, nullptr, &D, &L, nullptr));
-    }
-    Downconverter(const Downconverter&) = delete;
-    ~Downconverter()
-    {
-        if (q) ldsp_ddc_destroy(q);
     }
     void reset() { check(ldsp_ddc_reset(q)); }
     unsigned ntuners()
@@ -1128,12 +1081,7 @@ struct Downconverter {
         check(ldsp_ddc_get_taps(q, h.mutable_data()));
         return h;
     }
-    float get_scale()
-    {
-        float s;
-        check(ldsp_ddc_get_scale(q, &s));
-        return s;
-    }
+    float get_scale() { return get_value<float>(ldsp_ddc_get_scale, q); }
     void set_scale(float s) { check(ldsp_ddc_set_scale(q, s)); }
     unsigned skip()
     {
@@ -1154,31 +1102,13 @@ struct Downconverter {
         return c;
     }
     void seek(uint64_t T) { check(ldsp_debug_ddc_seek(q, T)); }
-    // iq16: the input is int16 (I, Q) pairs, converted by the kernel's loads (ldsp_ddc_execute_iq16)
-    py::object run(const CallIn& in, bool iq16)
+    py::object run(const py::handle& x, bool iq16)
     {
-        const auto exec = iq16 ? ldsp_ddc_execute_iq16 : ldsp_ddc_execute;
-        size_t nw = 0;
-        const unsigned C = ntuners();
-        const size_t K = num_outputs(in.n);
-        if (in.dev) {
-            py::object out = dev_empty2(C, K, true, in.device);
-            check(exec(q, in.ptr, in.n, tptr(out), K, &nw, LDSP_MEM_DEVICE, in.stream));
-            return out;
-        }
-        py::array_t<cf> out({(py::ssize_t)C, (py::ssize_t)K});
-        void* yp = out.mutable_data();
-        int rc;
-        {
-            py::gil_scoped_release rel;
-            rc = exec(q, in.ptr, in.n, yp, K, &nw, LDSP_MEM_HOST, nullptr);
-        }
-        check(rc);
-        return std::move(out);
+        return run_to_rows(q.get(), x, iq16, ntuners(), ldsp_ddc_num_outputs, ldsp_ddc_execute, ldsp_ddc_execute_iq16);
     }
-    py::object call(const py::handle& x) { return run(cplx_in(x), false); }
+    py::object call(const py::handle& x) { return run(x, false); }
     // self(bytes_to_iq(raw)) without the complex64 copy: raw as ComplexIIRFilter.from_bytes takes it
-    py::object from_bytes(const py::handle& b) { return run(raw_in(b), true); }
+    py::object from_bytes(const py::handle& b) { return run(b, true); }
 };
 
 // ------------------------------------------------------------------ FMBank (liquid: freqdem + firdecim_rrrf per row)
@@ -1187,7 +1117,7 @@ struct Downconverter {
 // and whose rows do not overlap (a block of rows or a range of columns of a
 // Channelizer or Downconverter output) is read in place.
 struct FMBank {
-    ldsp_fmbank_t q = nullptr;
+    Handle<ldsp_fmbank_t, ldsp_fmbank_destroy> q;
     unsigned C = 0, D = 0, L = 0;
     float kf;
     FMBank(int nchan, float kf_, int decim, int m, const py::object& fc, float as, const py::object& taps) : kf(kf_)
@@ -1196,22 +1126,13 @@ struct FMBank {
         if (decim < 0) throw py::value_error("FMBank: decim must lie in 1 .. 64");
         if (!taps.is_none()) {
             std::vector<float> h = to_fvec(taps);
-            check(ldsp_fmbank_create_taps((unsigned)nchan, kf, (unsigned)decim, h.data(), (unsigned)h.size(), &q));
+            check(ldsp_fmbank_create_taps((unsigned)nchan, kf, (unsigned)decim, h.data(), (unsigned)h.size(), q.out()));
         } else {
             if (m < 0) throw py::value_error("FMBank: m must be >= 1");
-            float c = 0.0f;                                   // the C ABI's default: 0.5 / decim
-            if (!fc.is_none()) {
-                c = fc.cast<float>();
-                if (!(c > 0.0f && c < 0.5f)) throw py::value_error("FMBank: Fc must lie in (0, 0.5)");
-            }
-            check(ldsp_fmbank_create((unsigned)nchan, kf, (unsigned)decim, (unsigned)m, c, as, &q));
+            const float c = opt_cutoff(fc, "FMBank");         // the C ABI's default: 0.5 / decim
+            check(ldsp_fmbank_create((unsigned)nchan, kf, (unsigned)decim, (unsigned)m, c, as, q.out()));
         }
         check(ldsp_fmbank_get_info(q, &C, &D, &L, nullptr));
-    }
-    FMBank(const FMBank&) = delete;
-    ~FMBank()
-    {
-        if (q) ldsp_fmbank_destroy(q);
     }
     void reset() { check(ldsp_fmbank_reset(q)); }
     py::array_t<float> taps()
@@ -1220,12 +1141,7 @@ struct FMBank {
         if (L) check(ldsp_fmbank_get_taps(q, h.mutable_data()));
         return h;
     }
-    float get_scale()
-    {
-        float s;
-        check(ldsp_fmbank_get_scale(q, &s));
-        return s;
-    }
+    float get_scale() { return get_value<float>(ldsp_fmbank_get_scale, q); }
     void set_scale(float s) { check(ldsp_fmbank_set_scale(q, s)); }
     unsigned skip()
     {
@@ -1245,64 +1161,10 @@ struct FMBank {
         check(ldsp_fmbank_num_outputs(q, K, &c));
         return c;
     }
-    void check_rows(py::ssize_t ndim, py::ssize_t rows) const
-    {
-        if (ndim != 2) throw py::value_error("FMBank: the input must be 2-D, [nchan, K] (1-D when nchan is 1)");
-        if (rows != (py::ssize_t)C)
-            throw py::value_error("FMBank: the input has " + std::to_string(rows) + " rows, nchan is " +
-                                  std::to_string(C));
-    }
     py::object call(const py::handle& x)
     {
-        size_t nw = 0;
-        if (is_device_tensor(x)) {
-            py::object& torch = torch_mod();
-            py::object t = py::reinterpret_borrow<py::object>(x);
-            if (C == 1 && t.attr("dim")().cast<int>() == 1) t = t.attr("unsqueeze")(0);
-            check_rows(t.attr("dim")().cast<py::ssize_t>(), t.attr("dim")().cast<int>() == 2
-                                                                ? t.attr("size")(0).cast<py::ssize_t>()
-                                                                : 0);
-            if (!py::object(t.attr("dtype")).equal(torch.attr("complex64"))) t = t.attr("to")(torch.attr("complex64"));
-            const size_t K = t.attr("size")(1).cast<size_t>();
-            // read in place: columns one sample apart, rows that do not overlap
-            if (K > 1 && t.attr("stride")(1).cast<long>() != 1)
-                throw py::value_error("FMBank: the input's columns must be one sample apart (stride(1) == 1)");
-            if (C > 1 && t.attr("stride")(0).cast<long>() < (long)K)
-                throw py::value_error("FMBank: the input's row stride must be at least its number of columns");
-            const size_t ldx = C > 1 ? t.attr("stride")(0).cast<size_t>() : K;
-            py::object device = t.attr("device");
-            const int tdev = device.attr("index").cast<int>();
-            const int cur = torch.attr("cuda").attr("current_device")().cast<int>();
-            if (tdev != cur)
-                throw py::value_error("input tensor is on cuda:" + std::to_string(tdev) +
-                                      " but the current device is cuda:" + std::to_string(cur) +
-                                      " (call under torch.cuda.device(" + std::to_string(tdev) + "))");
-            void* stream = reinterpret_cast<void*>(
-                torch.attr("cuda").attr("current_stream")(device).attr("cuda_stream").cast<uintptr_t>());
-            const size_t N = num_outputs(K);
-            py::dict kw;
-            kw["dtype"] = torch.attr("float32");
-            kw["device"] = device;
-            py::object out = torch.attr("empty")(py::make_tuple(C, N), **kw);
-            check(ldsp_fmbank_execute(q, tptr(t), ldx, K, tptr(out), N, &nw, LDSP_MEM_DEVICE, stream));
-            return out;
-        }
-        carr a = carr::ensure(x);
-        if (!a) throw py::error_already_set();
-        if (C == 1 && a.ndim() == 1) a = a.reshape({(py::ssize_t)1, a.shape(0)});
-        check_rows(a.ndim(), a.ndim() == 2 ? a.shape(0) : 0);
-        const size_t K = (size_t)a.shape(1);
-        const size_t N = num_outputs(K);
-        py::array_t<float> out({(py::ssize_t)C, (py::ssize_t)N});
-        void* yp = out.mutable_data();
-        const void* xp = a.data();
-        int rc;
-        {
-            py::gil_scoped_release rel;
-            rc = ldsp_fmbank_execute(q, xp, K, K, yp, N, &nw, LDSP_MEM_HOST, nullptr);
-        }
-        check(rc);
-        return out;
+        return run_from_rows(q.get(), in_rows(x, Kind::c64, C, "FMBank", true, Strided::refuse), Kind::f32, C,
+                             ldsp_fmbank_num_outputs, ldsp_fmbank_execute);
     }
 };
 
@@ -1312,7 +1174,7 @@ struct FMBank {
 // one sample apart and whose rows do not overlap (an FMBank output, a block of
 // rows or a range of columns of one) is read in place.
 struct AudioBank {
-    ldsp_audiobank_t q = nullptr;
+    Handle<ldsp_audiobank_t, ldsp_audiobank_destroy> q;
     unsigned C = 0, m = 0, npfb = 0;
     float rate;
     bool pcm;
@@ -1330,14 +1192,9 @@ struct AudioBank {
             if (!(sr > 0.0f)) throw py::value_error("AudioBank: deemphasis (the rows' sample rate) must be > 0");
         }
         check(ldsp_audiobank_create((unsigned)nchan, rate, (unsigned)len, c, as, (unsigned)nfilter, sr, tau,
-                                    pcm16 ? 1 : 0, &q));
+                                    pcm16 ? 1 : 0, q.out()));
         m = (unsigned)len;
         check(ldsp_audiobank_get_info(q, &C, &npfb, nullptr, nullptr, nullptr));
-    }
-    AudioBank(const AudioBank&) = delete;
-    ~AudioBank()
-    {
-        if (q) ldsp_audiobank_destroy(q);
     }
     void reset() { check(ldsp_audiobank_reset(q)); }
     uint32_t step()
@@ -1378,12 +1235,7 @@ struct AudioBank {
         check(ldsp_audiobank_get_coefs(q, c.mutable_data(), c.mutable_data() + 1, nullptr, nullptr));
         return py::make_tuple(c[py::int_(0)], c[py::int_(1)]);
     }
-    float get_scale()
-    {
-        float s;
-        check(ldsp_audiobank_get_scale(q, &s));
-        return s;
-    }
+    float get_scale() { return get_value<float>(ldsp_audiobank_get_scale, q); }
     void set_scale(float s) { check(ldsp_audiobank_set_scale(q, s)); }
     size_t tile()
     {
@@ -1397,65 +1249,10 @@ struct AudioBank {
         check(ldsp_audiobank_num_outputs(q, K, &c));
         return c;
     }
-    void check_rows(py::ssize_t ndim, py::ssize_t rows) const
-    {
-        if (ndim != 2) throw py::value_error("AudioBank: the input must be 2-D, [nchan, K] (1-D when nchan is 1)");
-        if (rows != (py::ssize_t)C)
-            throw py::value_error("AudioBank: the input has " + std::to_string(rows) + " rows, nchan is " +
-                                  std::to_string(C));
-    }
     py::object call(const py::handle& x)
     {
-        size_t nw = 0;
-        if (is_device_tensor(x)) {
-            py::object& torch = torch_mod();
-            py::object t = py::reinterpret_borrow<py::object>(x);
-            if (C == 1 && t.attr("dim")().cast<int>() == 1) t = t.attr("unsqueeze")(0);
-            check_rows(t.attr("dim")().cast<py::ssize_t>(), t.attr("dim")().cast<int>() == 2
-                                                                ? t.attr("size")(0).cast<py::ssize_t>()
-                                                                : 0);
-            if (!py::object(t.attr("dtype")).equal(torch.attr("float32"))) t = t.attr("to")(torch.attr("float32"));
-            const size_t K = t.attr("size")(1).cast<size_t>();
-            // read in place: columns one sample apart, rows that do not overlap
-            if (K > 1 && t.attr("stride")(1).cast<long>() != 1)
-                throw py::value_error("AudioBank: the input's columns must be one sample apart (stride(1) == 1)");
-            if (C > 1 && t.attr("stride")(0).cast<long>() < (long)K)
-                throw py::value_error("AudioBank: the input's row stride must be at least its number of columns");
-            const size_t ldx = C > 1 ? t.attr("stride")(0).cast<size_t>() : K;
-            py::object device = t.attr("device");
-            const int tdev = device.attr("index").cast<int>();
-            const int cur = torch.attr("cuda").attr("current_device")().cast<int>();
-            if (tdev != cur)
-                throw py::value_error("input tensor is on cuda:" + std::to_string(tdev) +
-                                      " but the current device is cuda:" + std::to_string(cur) +
-                                      " (call under torch.cuda.device(" + std::to_string(tdev) + "))");
-            void* stream = reinterpret_cast<void*>(
-                torch.attr("cuda").attr("current_stream")(device).attr("cuda_stream").cast<uintptr_t>());
-            const size_t N = num_outputs(K);
-            py::dict kw;
-            kw["dtype"] = pcm ? torch.attr("int16") : torch.attr("float32");
-            kw["device"] = device;
-            py::object out = torch.attr("empty")(py::make_tuple(C, N), **kw);
-            check(ldsp_audiobank_execute(q, tptr(t), ldx, K, tptr(out), N, &nw, LDSP_MEM_DEVICE, stream));
-            return out;
-        }
-        farr a = farr::ensure(x);
-        if (!a) throw py::error_already_set();
-        if (C == 1 && a.ndim() == 1) a = a.reshape({(py::ssize_t)1, a.shape(0)});
-        check_rows(a.ndim(), a.ndim() == 2 ? a.shape(0) : 0);
-        const size_t K = (size_t)a.shape(1);
-        const size_t N = num_outputs(K);
-        py::array out = pcm ? py::array(py::array_t<int16_t>({(py::ssize_t)C, (py::ssize_t)N}))
-                            : py::array(py::array_t<float>({(py::ssize_t)C, (py::ssize_t)N}));
-        void* yp = out.mutable_data();
-        const void* xp = a.data();
-        int rc;
-        {
-            py::gil_scoped_release rel;
-            rc = ldsp_audiobank_execute(q, xp, K, K, yp, N, &nw, LDSP_MEM_HOST, nullptr);
-        }
-        check(rc);
-        return out;
+        return run_from_rows(q.get(), in_rows(x, Kind::f32, C, "AudioBank", true, Strided::refuse),
+                             pcm ? Kind::i16 : Kind::f32, C, ldsp_audiobank_num_outputs, ldsp_audiobank_execute);
     }
 };
 
@@ -1464,7 +1261,7 @@ struct AudioBank {
 // row k mixed up to k / nchan.  A device tensor whose columns are contiguous (a
 // block of rows or a range of columns of a Channelizer output) is read in place.
 struct Synthesizer {
-    ldsp_synth_t q = nullptr;
+    Handle<ldsp_synth_t, ldsp_synth_destroy> q;
     unsigned M = 0, D = 0, L = 0;
     Synthesizer(int nchan, const py::object& interp, int m, const py::object& fc, float as, const py::object& taps)
     {
@@ -1473,22 +1270,13 @@ struct Synthesizer {
         if (d < 0) throw py::value_error("Synthesizer: interp must be nchan or nchan // 2");
         if (!taps.is_none()) {
             std::vector<float> g = to_fvec(taps);
-            check(ldsp_synth_create_taps((unsigned)nchan, (unsigned)d, g.data(), (unsigned)g.size(), &q));
+            check(ldsp_synth_create_taps((unsigned)nchan, (unsigned)d, g.data(), (unsigned)g.size(), q.out()));
         } else {
             if (m < 0) throw py::value_error("Synthesizer: m must be >= 1");
-            float f = 0.0f;                                   // the C ABI's default: 1 / nchan or 0.5 / nchan
-            if (!fc.is_none()) {
-                f = fc.cast<float>();
-                if (!(f > 0.0f && f < 0.5f)) throw py::value_error("Synthesizer: Fc must lie in (0, 0.5)");
-            }
-            check(ldsp_synth_create((unsigned)nchan, (unsigned)d, (unsigned)m, f, as, &q));
+            const float f = opt_cutoff(fc, "Synthesizer");    // the C ABI's default: 1 / nchan or 0.5 / nchan
+            check(ldsp_synth_create((unsigned)nchan, (unsigned)d, (unsigned)m, f, as, q.out()));
         }
         check(ldsp_synth_get_info(q, &M, &D, &L));
-    }
-    Synthesizer(const Synthesizer&) = delete;
-    ~Synthesizer()
-    {
-        if (q) ldsp_synth_destroy(q);
     }
     void reset() { check(ldsp_synth_reset(q)); }
     py::array_t<float> taps()
@@ -1497,12 +1285,7 @@ struct Synthesizer {
         check(ldsp_synth_get_taps(q, g.mutable_data()));
         return g;
     }
-    float get_scale()
-    {
-        float s;
-        check(ldsp_synth_get_scale(q, &s));
-        return s;
-    }
+    float get_scale() { return get_value<float>(ldsp_synth_get_scale, q); }
     void set_scale(float s) { check(ldsp_synth_set_scale(q, s)); }
     size_t tile()
     {
@@ -1510,69 +1293,17 @@ struct Synthesizer {
         check(ldsp_debug_synth_tile(M, D, &f));
         return f;
     }
-    py::array_t<double> centers()
-    {
-        py::array_t<double> c(M);
-        for (unsigned k = 0; k < M; k++) c.mutable_at(k) = std::fmod((double)k / M + 0.5, 1.0) - 0.5;
-        return c;
-    }
+    py::array_t<double> centers() { return wrapped_centers(M); }
     size_t num_outputs(size_t K)
     {
         size_t n = 0;
         check(ldsp_synth_num_outputs(q, K, &n));
         return n;
     }
-    void check_rows(py::ssize_t ndim, py::ssize_t rows) const
-    {
-        if (ndim != 2) throw py::value_error("Synthesizer: the input must be 2-D, [nchan, K]");
-        if (rows != (py::ssize_t)M)
-            throw py::value_error("Synthesizer: the input has " + std::to_string(rows) + " rows, nchan is " +
-                                  std::to_string(M));
-    }
     py::object call(const py::handle& x)
     {
-        size_t nw = 0;
-        if (is_device_tensor(x)) {
-            py::object& torch = torch_mod();
-            py::object t = py::reinterpret_borrow<py::object>(x);
-            check_rows(t.attr("dim")().cast<py::ssize_t>(), t.attr("dim")().cast<int>() == 2
-                                                                ? t.attr("size")(0).cast<py::ssize_t>()
-                                                                : 0);
-            if (!py::object(t.attr("dtype")).equal(torch.attr("complex64"))) t = t.attr("to")(torch.attr("complex64"));
-            const size_t K = t.attr("size")(1).cast<size_t>();
-            // columns one sample apart and rows that do not overlap: read in place
-            if (t.attr("stride")(1).cast<long>() != 1 || t.attr("stride")(0).cast<long>() < (long)K)
-                t = t.attr("contiguous")();
-            const size_t ld = std::max<size_t>(t.attr("stride")(0).cast<size_t>(), K);
-            py::object device = t.attr("device");
-            const int tdev = device.attr("index").cast<int>();
-            const int cur = torch.attr("cuda").attr("current_device")().cast<int>();
-            if (tdev != cur)
-                throw py::value_error("input tensor is on cuda:" + std::to_string(tdev) +
-                                      " but the current device is cuda:" + std::to_string(cur) +
-                                      " (call under torch.cuda.device(" + std::to_string(tdev) + "))");
-            void* stream = reinterpret_cast<void*>(
-                torch.attr("cuda").attr("current_stream")(device).attr("cuda_stream").cast<uintptr_t>());
-            const size_t N = num_outputs(K);
-            py::object out = dev_empty(N, true, device);
-            check(ldsp_synth_execute(q, tptr(t), ld, K, tptr(out), N, &nw, LDSP_MEM_DEVICE, stream));
-            return out;
-        }
-        carr a = carr::ensure(x);
-        if (!a) throw py::error_already_set();
-        check_rows(a.ndim(), a.ndim() == 2 ? a.shape(0) : 0);
-        const size_t K = (size_t)a.shape(1);
-        const size_t N = num_outputs(K);
-        py::array out = host_array(N, true);
-        void* zp = out.mutable_data();
-        const void* yp = a.data();
-        int rc;
-        {
-            py::gil_scoped_release rel;
-            rc = ldsp_synth_execute(q, yp, K, K, zp, N, &nw, LDSP_MEM_HOST, nullptr);
-        }
-        check(rc);
-        return out;
+        return run_from_rows(q.get(), in_rows(x, Kind::c64, M, "Synthesizer", false, Strided::copy), Kind::c64, -1,
+                             ldsp_synth_num_outputs, ldsp_synth_execute);
     }
 };
 
@@ -1581,7 +1312,7 @@ struct Synthesizer {
 // r the mean of `average` transforms' power per bin in FFT order, plus a running
 // float64 mean of every transform (psd).
 struct Spectrogram {
-    ldsp_spgram_t q = nullptr;
+    Handle<ldsp_spgram_t, ldsp_spgram_destroy> q;
     unsigned N = 0, W = 0, D = 0, A = 0;
     Spectrogram(long nfft, const py::object& window, const py::object& window_len, const py::object& delay,
                 long average)
@@ -1599,18 +1330,13 @@ struct Spectrogram {
             else if (name == "hann") wt = LDSP_WIN_HANN;
             else if (name == "hamming") wt = LDSP_WIN_HAMMING;
             else if (name == "blackmanharris") wt = LDSP_WIN_BLACKMANHARRIS;
-            check(ldsp_spgram_create((unsigned)nfft, wt, (unsigned)wl, (unsigned)d, (unsigned)average, &q));
+            check(ldsp_spgram_create((unsigned)nfft, wt, (unsigned)wl, (unsigned)d, (unsigned)average, q.out()));
         } else {
             std::vector<float> w = to_fvec(window);
             if ((long)w.size() != wl) throw py::value_error("Spectrogram: the window array's length must be window_len");
-            check(ldsp_spgram_create_window((unsigned)nfft, w.data(), (unsigned)wl, (unsigned)d, (unsigned)average, &q));
+            check(ldsp_spgram_create_window((unsigned)nfft, w.data(), (unsigned)wl, (unsigned)d, (unsigned)average, q.out()));
         }
         check(ldsp_spgram_get_info(q, &N, &W, &D, &A, nullptr, nullptr));
-    }
-    Spectrogram(const Spectrogram&) = delete;
-    ~Spectrogram()
-    {
-        if (q) ldsp_spgram_destroy(q);
     }
     void reset() { check(ldsp_spgram_reset(q)); }
     void clear() { check(ldsp_spgram_clear(q)); }
@@ -1638,12 +1364,7 @@ struct Spectrogram {
         check(ldsp_debug_spgram_tile(N, &f));
         return f;
     }
-    py::array_t<double> freqs()
-    {
-        py::array_t<double> c(N);
-        for (unsigned k = 0; k < N; k++) c.mutable_at(k) = std::fmod((double)k / N + 0.5, 1.0) - 0.5;
-        return c;
-    }
+    py::array_t<double> freqs() { return wrapped_centers(N); }
     py::array_t<double> psd()
     {
         py::array_t<double> p(N);
@@ -1664,37 +1385,23 @@ struct Spectrogram {
     }
     // rows: store them and return the image; otherwise accumulate only and return the transforms taken.
     // iq16: the input is int16 (I, Q) pairs, converted by the kernel's loads (ldsp_spgram_execute_iq16)
-    py::object run(const CallIn& in, bool rows, bool iq16)
+    py::object run(const py::handle& x, bool rows, bool iq16)
     {
         const auto exec = iq16 ? ldsp_spgram_execute_iq16 : ldsp_spgram_execute;
+        const CallIn in = in_1d(x, iq16 ? Kind::i16 : Kind::c64);
         size_t nt = 0, K = 0, nw = 0;
         check(ldsp_spgram_num_outputs(q, in.n, &nt, &K));
-        if (in.dev) {
-            py::object out;
-            float* yp = nullptr;
-            if (rows) {
-                out = dev_empty2(K, N, false, in.device);
-                yp = (float*)tptr(out);
-            }
-            check(exec(q, in.ptr, in.n, yp, N, &nw, LDSP_MEM_DEVICE, in.stream));
-            return rows ? out : py::object(py::int_(nt));
-        }
-        py::array_t<float> out({(py::ssize_t)(rows ? K : 0), (py::ssize_t)N});
-        float* yp = rows ? out.mutable_data() : nullptr;
-        int rc;
-        {
-            py::gil_scoped_release rel;
-            rc = exec(q, in.ptr, in.n, yp, N, &nw, LDSP_MEM_HOST, nullptr);
-        }
-        check(rc);
-        return rows ? py::object(out) : py::object(py::int_(nt));
+        CallOut out;
+        if (rows) out = make_out(in, Kind::f32, K, N);
+        invoke(in, [&](int mem, void* s) { return exec(q, in.ptr, in.n, (float*)out.ptr, N, &nw, mem, s); });
+        return rows ? out.obj : py::object(py::int_(nt));
     }
-    py::object call(const py::handle& x) { return run(cplx_in(x), true, false); }
-    py::object write(const py::handle& x) { return run(cplx_in(x), false, false); }
+    py::object call(const py::handle& x) { return run(x, true, false); }
+    py::object write(const py::handle& x) { return run(x, false, false); }
     // self(bytes_to_iq(raw)) / self.write(bytes_to_iq(raw)) without the complex64
     // copy: raw as ComplexIIRFilter.from_bytes takes it
-    py::object from_bytes(const py::handle& b) { return run(raw_in(b), true, true); }
-    py::object write_bytes(const py::handle& b) { return run(raw_in(b), false, true); }
+    py::object from_bytes(const py::handle& b) { return run(b, true, true); }
+    py::object write_bytes(const py::handle& b) { return run(b, false, true); }
 };
 
 // SSBDemod (demod.hpp:155-187): firhilbf_create(25, 60), c2r, one sideband kept
@@ -1703,7 +1410,7 @@ struct SSBDemod {
     Hilb h;
     explicit SSBDemod(const std::string& band) : usb(band == "usb"), h(25, 60.0f, LDSP_HILB_C2R) {}
     void reset() { check(ldsp_firhilb_reset(h.q)); }
-    py::object call(const py::handle& x) { return h.run(x, true, false, &Hilb::same, false, usb); }
+    py::object call(const py::handle& x) { return h.run(x, Kind::c64, Kind::f32, &Hilb::same, false, usb); }
 };
 
 // HilbertTransform (utility.hpp:71-108): one firhilbf per direction, each with
@@ -1731,23 +1438,16 @@ struct HilbertTransform {
         for (auto& h : o)
             if (h) check(ldsp_firhilb_reset(h->q));
     }
-    py::object interp(const py::handle& x) { return get(LDSP_HILB_INTERP).run(x, true, false, &Hilb::twice); }
-    py::object decim(const py::handle& x) { return get(LDSP_HILB_DECIM).run(x, false, true, &Hilb::half); }
-    py::object r2c(const py::handle& x) { return get(LDSP_HILB_R2C).run(x, false, true, &Hilb::same); }
-    py::object c2r(const py::handle& x) { return get(LDSP_HILB_C2R).run(x, true, false, &Hilb::same, true); }
+    py::object interp(const py::handle& x) { return get(LDSP_HILB_INTERP).run(x, Kind::c64, Kind::f32, &Hilb::twice); }
+    py::object decim(const py::handle& x) { return get(LDSP_HILB_DECIM).run(x, Kind::f32, Kind::c64, &Hilb::half); }
+    py::object r2c(const py::handle& x) { return get(LDSP_HILB_R2C).run(x, Kind::f32, Kind::c64, &Hilb::same); }
+    py::object c2r(const py::handle& x) { return get(LDSP_HILB_C2R).run(x, Kind::c64, Kind::f32, &Hilb::same, true); }
     // dispatch on dtype like Delay: complex64 -> interp, float32 -> decim, anything else -> None
     py::object call(const py::handle& x)
     {
-        py::object tp = py::getattr(x, "dtype");
-        if (is_device_tensor(x)) {
-            py::object& torch = torch_mod();
-            if (tp.equal(torch.attr("complex64"))) return interp(x);
-            if (tp.equal(torch.attr("float32"))) return decim(x);
-        } else {
-            if (tp.equal(py::dtype("complex64"))) return interp(x);
-            if (tp.equal(py::dtype("float32"))) return decim(x);
-        }
-        return py::none();
+        Kind k;
+        if (!kind_from_dtype(x, &k)) return py::none();
+        return k == Kind::c64 ? interp(x) : decim(x);
     }
 };
 
@@ -1755,28 +1455,20 @@ struct HilbertTransform {
 // device tensor -> complex64 device tensor
 py::object bytes_to_iq(const py::handle& b)
 {
+    CallIn in;          // n counts bytes here; the device of a tensor is not checked
+    py::buffer_info bi;
     if (is_device_tensor(b)) {
-        py::object& torch = torch_mod();
         py::object t = py::reinterpret_borrow<py::object>(b).attr("reshape")(-1).attr("contiguous")();
-        const size_t nbytes = t.attr("numel")().cast<size_t>() * t.attr("element_size")().cast<size_t>();
-        py::object dev = t.attr("device");
-        void* s = reinterpret_cast<void*>(
-            torch.attr("cuda").attr("current_stream")(dev).attr("cuda_stream").cast<uintptr_t>());
-        py::object out = dev_empty(nbytes / 4, true, dev);
-        check(ldsp_bytes_to_iq(tptr(t), nbytes, tptr(out), LDSP_MEM_DEVICE, s));
-        return out;
+        on_device(in, t, DevCheck::none);
+        in.n = t.attr("numel")().cast<size_t>() * t.attr("element_size")().cast<size_t>();
+    } else {
+        bi = py::reinterpret_borrow<py::buffer>(b).request();
+        in.ptr = bi.ptr;
+        in.n = (size_t)bi.size * (size_t)bi.itemsize;
     }
-    py::buffer_info bi = py::reinterpret_borrow<py::buffer>(b).request();
-    const size_t nbytes = (size_t)bi.size * (size_t)bi.itemsize;
-    py::array_t<cf> out = host_array<cf>(nbytes / 4);
-    void* yp = out.mutable_data();
-    int rc;
-    {
-        py::gil_scoped_release rel;
-        rc = ldsp_bytes_to_iq(bi.ptr, nbytes, yp, LDSP_MEM_HOST, nullptr);
-    }
-    check(rc);
-    return std::move(out);
+    CallOut out = make_out(in, Kind::c64, in.n / 4);
+    invoke(in, [&](int mem, void* s) { return ldsp_bytes_to_iq(in.ptr, in.n, out.ptr, mem, s); });
+    return out.obj;
 }
 
 // distinct C++ types for the distinct Python classes
@@ -1912,32 +1604,8 @@ void bind_proto(py::module_& m, const char* name)
         .def_readonly("F0", &C::mF0)
         .def_readonly("Ap", &C::mAp)
         .def_readonly("As", &C::mAs)
-        .def("freqresponse", &C::freqresponse)
-        .def("__call__", &C::call)
-        .def("from_bytes", &C::from_bytes, py::arg("byts"),
-             "self(bytes_to_iq(byts)) in one pass: int16 (I, Q) pairs converted on load (complex filters)")
-        .def("print", &C::print)
-        .def("reset", &C::reset)
-        .def_property("exact", &C::get_exact, &C::set_exact)
-        .def("sos", &C::sos)
-        .def("_scan_path", [](C& c, int path) { check(ldsp_debug_iir_path(c.q, path)); },
-             "test hook: 0 automatic, 1 blocked scan, 2 modal scan")
-        .def("_modal_info", [](C& c) {
-            int ok = 0, m = 0, j = 0;
-            double err = 0;
-            check(ldsp_debug_iir_modal_info(c.q, &ok, &m, &j, &err));
-            return py::make_tuple(ok != 0, m, j, err);
-        })
-        .def("_modal_grid", [](C& c, size_t n) {
-            long units = 0;
-            int onex = 0;
-            unsigned grid = 0;
-            check(ldsp_debug_iir_modal_grid(c.q, n, &units, &onex, &grid));
-            return py::make_tuple(units, onex != 0, grid);
-        }, py::arg("n"),
-             "test hook (host logic only): (units, one-XCD mode, workgroups) of a modal-scan call of n samples "
-             "(ldsp_debug_iir_modal_grid)")
-        .def("_dispatch", &iir_dispatch<C>, py::arg("n"), kIirDispatchDoc);
+        .def("print", &C::print);
+    bind_iir_common<C>(c);
 }
 
 const char* kResampDoc = "Arbitrary-rate polyphase resampler (liquid resamp_*), runs on the GPU.";
@@ -2095,7 +1763,7 @@ PYBIND11_MODULE(_liquiddsp, m)
     m.def(
         "mix_down_filter",
         [](NCO& nco, ComplexFIRFilter& fir, const py::handle& x) {
-            return run_same(x, true, true, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
+            return run_same(x, Kind::c64, Kind::c64, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
                 return ldsp_nco_mix_firfilt(nco.q, fir.q, xi, n, yo, 1, mem, s);
             });
         },
@@ -2104,7 +1772,7 @@ PYBIND11_MODULE(_liquiddsp, m)
     m.def(
         "mix_up_filter",
         [](NCO& nco, ComplexFIRFilter& fir, const py::handle& x) {
-            return run_same(x, true, true, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
+            return run_same(x, Kind::c64, Kind::c64, [&](const void* xi, size_t n, void* yo, int mem, void* s) {
                 return ldsp_nco_mix_firfilt(nco.q, fir.q, xi, n, yo, 0, mem, s);
             });
         },
@@ -2117,33 +1785,8 @@ PYBIND11_MODULE(_liquiddsp, m)
         [](py::object iir_o, py::object rs_o, const py::handle& x) {
             IIR& iir = as_iir(iir_o);
             Resampler& rs = as_resampler(rs_o);
-            const bool c = rs.cplx;
-            if (iir.cplx != c) throw py::value_error("filter_resample: the filter and the resampler must both be complex or both real");
-            if (is_device_tensor(x)) {
-                DevIn d = dev_in(x, c);
-                size_t nout = 0;
-                check(ldsp_resamp_num_outputs(rs.q, d.n, &nout));
-                py::object out = dev_empty(nout, c, d.device);
-                size_t nw = 0;
-                check(ldsp_iirfilt_resamp_execute(iir.q, rs.q, d.ptr, d.n, tptr(out), nout, &nw, LDSP_MEM_DEVICE, d.stream));
-                return out;
-            }
-            py::array a = c ? py::array(carr::ensure(x)) : py::array(farr::ensure(x));
-            if (!a) throw py::error_already_set();
-            const size_t n = (size_t)a.size();
-            size_t nout = 0;
-            check(ldsp_resamp_num_outputs(rs.q, n, &nout));
-            py::array out = host_array(nout, c);
-            void* yp = out.mutable_data();
-            const void* xp = a.data();
-            size_t nw = 0;
-            int rc;
-            {
-                py::gil_scoped_release rel;
-                rc = ldsp_iirfilt_resamp_execute(iir.q, rs.q, xp, n, yp, nout, &nw, LDSP_MEM_HOST, nullptr);
-            }
-            check(rc);
-            return py::object(out);
+            if (iir.cplx != rs.cplx) throw py::value_error("filter_resample: the filter and the resampler must both be complex or both real");
+            return rs.run(x, iir.q);
         },
         py::arg("iir"), py::arg("resampler"), py::arg("x"),
         "resampler(iir(x)) in one pass (the filter's outputs stay on chip when it takes the fast modal scan): "
@@ -2157,14 +1800,8 @@ PYBIND11_MODULE(_liquiddsp, m)
             const size_t C = py::len(objs);
             if (C == 0) return py::list();
             if (py::len(xs) != C) throw py::value_error("execute_many: one input per object");
-            std::vector<DevIn> ins;
-            for (size_t c = 0; c < C; c++) {
-                if (!is_device_tensor(xs[c])) throw py::value_error("execute_many: device tensors only");
-                ins.push_back(dev_in(xs[c], true));
-                if (ins[c].n != ins[0].n) throw py::value_error("execute_many: every input must have the same length");
-                if (!ins[c].device.equal(ins[0].device))
-                    throw py::value_error("execute_many: every input must be on the same device");
-            }
+            std::vector<CallIn> ins;
+            for (size_t c = 0; c < C; c++) many_in(ins, xs[c], Kind::c64, "execute_many");
             const size_t n = ins[0].n;
             py::object o0 = objs[0];
             std::vector<const void*> xp;
@@ -2173,9 +1810,9 @@ PYBIND11_MODULE(_liquiddsp, m)
             std::vector<void*> yp;
             auto mk = [&](bool cout) {
                 for (size_t c = 0; c < C; c++) {
-                    py::object t = dev_empty(n, cout, ins[c].device);
-                    yp.push_back(tptr(t));
-                    outs.append(t);
+                    CallOut o = make_out(ins[c], kind_of(cout), n);
+                    yp.push_back(o.ptr);
+                    outs.append(o.obj);
                 }
             };
             if (py::isinstance<AGC>(o0)) {
@@ -2205,7 +1842,7 @@ PYBIND11_MODULE(_liquiddsp, m)
                     ins.clear();
                     xp.clear();
                     for (size_t c = 0; c < C; c++) {
-                        ins.push_back(dev_in(xs[c], false));
+                        ins.push_back(in_1d(xs[c], Kind::f32));
                         xp.push_back(ins[c].ptr);
                     }
                 }
@@ -2225,7 +1862,7 @@ PYBIND11_MODULE(_liquiddsp, m)
             if (py::len(rss) != C || py::len(xs) != C) throw py::value_error("filter_resample_many: one resampler and input per filter");
             std::vector<ldsp_iirfilt_t> q;
             std::vector<ldsp_resamp_t> r;
-            std::vector<DevIn> ins;
+            std::vector<CallIn> ins;
             std::vector<const void*> xp;
             bool c0 = as_resampler(rss[0]).cplx;
             for (size_t c = 0; c < C; c++) {
@@ -2234,11 +1871,7 @@ PYBIND11_MODULE(_liquiddsp, m)
                 if (f.cplx != c0 || rs.cplx != c0) throw py::value_error("filter_resample_many: mixed real and complex");
                 q.push_back(f.q);
                 r.push_back(rs.q);
-                if (!is_device_tensor(xs[c])) throw py::value_error("filter_resample_many: device tensors only");
-                ins.push_back(dev_in(xs[c], c0));
-                if (ins[c].n != ins[0].n) throw py::value_error("filter_resample_many: every input must have the same length");
-                if (!ins[c].device.equal(ins[0].device))
-                    throw py::value_error("filter_resample_many: every input must be on the same device");
+                many_in(ins, xs[c], kind_of(c0), "filter_resample_many");
                 xp.push_back(ins[c].ptr);
             }
             const size_t n = ins[0].n;
@@ -2251,9 +1884,9 @@ PYBIND11_MODULE(_liquiddsp, m)
             py::list outs;
             std::vector<void*> yp;
             for (size_t c = 0; c < C; c++) {
-                py::object t = dev_empty(k[c], c0, ins[c].device);
-                yp.push_back(tptr(t));
-                outs.append(t);
+                CallOut o = make_out(ins[c], kind_of(c0), k[c]);
+                yp.push_back(o.ptr);
+                outs.append(o.obj);
             }
             std::vector<size_t> nout(C);
             check(ldsp_iirfilt_resamp_execute_many(q.data(), r.data(), xp.data(), n, yp.data(), cap, nout.data(),

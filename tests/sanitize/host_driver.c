@@ -361,6 +361,15 @@ static void no_device_calls(void)
         CHECK(ncols == 4 && ldsp_chan_reset(ch) == LDSP_OK && ldsp_chan_destroy(ch) == LDSP_OK);
     }
 
+    ldsp_fmbank_t fb = NULL;                                   /* the decimating prototype's checks */
+    CHECK(ldsp_fmbank_create(2, 0.25f, 4, 9, 0.0f, 60.0f, &fb) == LDSP_EUNSUP && fb == NULL);
+    static float ht[17 * 4 + 1];
+    CHECK(ldsp_fmbank_create_taps(2, 0.25f, 4, ht, 17 * 4 + 1, &fb) == LDSP_EUNSUP && fb == NULL);
+    CHECK(ldsp_fmbank_create(2, 0.25f, 4, 6, 0.0f, 60.0f, &fb) == LDSP_OK);
+    unsigned fskip = 9;
+    CHECK(ldsp_fmbank_get_info(fb, NULL, NULL, NULL, &fskip) == LDSP_OK && fskip == 0);
+    CHECK(ldsp_fmbank_destroy(fb) == LDSP_OK);
+
     ldsp_spgram_t sp = NULL;
     size_t nrows = 9;
     double psd[256];
