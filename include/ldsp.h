@@ -698,8 +698,9 @@ int ldsp_debug_ddc_seek(ldsp_ddc_t q, uint64_t T);
  * y + c * ldy (both in samples, ldx >= K); it sets *ncols and, when
  * ldy < *ncols, returns LDSP_ERANGE without consuming the input.  Argument
  * errors are decided on the host before any device work.
- * De-emphasis and rate conversion over the rows it writes: AudioBank, below.
- * Not built: squelch over rows, a per-row kf.
+ * De-emphasis and rate conversion over the rows it writes: AudioBank, below;
+ * a squelch over the rows it reads: SquelchBank, below.
+ * Not built: a per-row kf.
  * ---------------------------------------------------------------------- */
 typedef struct ldsp_fmbank_s *ldsp_fmbank_t;
 int ldsp_fmbank_create(unsigned int C, float kf, unsigned int D, unsigned int m, float fc, float as, ldsp_fmbank_t *q);
@@ -775,6 +776,82 @@ int ldsp_audiobank_execute(ldsp_audiobank_t q, const void *x, size_t ldx, size_t
                            int mem, void *stream);
 /* Test hook: outputs per workgroup of the kernel this object launches. */
 int ldsp_debug_audiobank_tile(ldsp_audiobank_t q, size_t *outputs);
+
+/* ------------------------------------------------------------------------
+ * SquelchBank: for every row of a complex64 [C][K] block (a Channelizer or
+ * Downconverter output, read in place), the row's smoothed power per block of
+ * B samples, liquid's squelch state per block and, optionally, the rows
+ * themselves with the closed blocks zeroed.  liquid's counterpart is the
+ * squelch half of agc_crcf, evaluated per block of samples instead of per
+ * sample and with no gain loop; the definition is this library's own.  For row
+ * c of the concatenated input x[c][t] (t counted from 0 since creation or
+ * reset), B = block, alpha = bandwidth (a double) and thr[c] the float32
+ * rounding of 10^(threshold_dB[c] / 10) computed in double:
+ *   p[c][b] = (1/B) sum_{i<B} |x[c][bB + i]|^2                     block power
+ *   s[c][b] = s[c][b-1] + alpha (p[c][b] - s[c][b-1]),  s[c][-1] = 0   (float64)
+ *   level[c][b] = (float) s[c][b]                        float32, linear power
+ *   hi = level[c][b] > thr[c]              in float32, on the value stored
+ *   mode[c][b] = liquid's agc squelch step from mode[c][b-1] with hi:
+ *     ENABLED(1):  hi ? RISE : ENABLED          RISE(2): hi ? SIGNALHI : FALL
+ *     SIGNALHI(3): hi ? SIGNALHI : FALL
+ *     FALL(4):     hi ? SIGNALHI : SIGNALLO, timer = timeout
+ *     SIGNALLO(5): --timer == 0 ? TIMEOUT : (hi ? SIGNALHI : SIGNALLO)
+ *     TIMEOUT(6):  ENABLED                      initial mode ENABLED, timer 0
+ *   status[c][b] = mode[c][b]                           uint8, liquid's codes
+ *   open = status in {RISE, SIGNALHI, FALL, SIGNALLO}
+ *   y[c][bB + i] = open ? x[c][bB + i] (the same bits) : +0.0
+ * The step is agc_squelch_update_mode, once per block: timeout counts blocks.
+ * The gate rule is this object's own: the reference's AGC wrapper zeroes
+ * SIGNALLO and passes TIMEOUT, which makes the time-out useless as a hang time;
+ * here SIGNALLO stays open and TIMEOUT is closed.  status is an exact function
+ * of the level output.
+ * Block b is emitted by the call that delivers its last sample: with T samples
+ * per row seen before a call, a call of K samples returns
+ * (T + K) / B - T / B blocks (integer division); K = 0 and calls too short for
+ * a block are allowed and carry state only.  The fill = (T + K) mod B samples of
+ * the unfinished block are carried to the next call, so the gated output of a
+ * call, complex64 [C][nblocks B], starts with the carried samples: the rows stay
+ * one contiguous stream, delayed to block boundaries.  A row's bits (level,
+ * status, gated samples) depend neither on how the stream is cut into calls,
+ * nor on the other rows, their number or order, nor on the row strides.
+ *   1 <= C <= 256, fixed at creation;  16 <= B <= 4096 (any integer);
+ *   0 < alpha <= 1;  timeout >= 1;  thresholds finite.
+ * Anything else (a NaN among them) is LDSP_EINVAL.
+ * ldsp_sqbank_create sets every row's threshold to threshold_dB;
+ * ldsp_sqbank_set_thresholds takes n = 1 (every row) or n = C values, takes
+ * effect at the next block and touches no state; ldsp_sqbank_reset restores the
+ * initial state and keeps the thresholds.
+ * ldsp_sqbank_execute reads row c at x + c * ldx (samples, ldx >= K) and writes
+ * row c of status to status + c * lds (bytes), of level to level + c * ldl
+ * (floats) and, where y is not NULL, of the gated samples to y + c * ldy
+ * (samples); with y == NULL it only measures.  It sets *nblocks and, when lds or
+ * ldl < *nblocks or ldy < *nblocks B, returns LDSP_ERANGE without consuming the
+ * input.  Argument errors are decided on the host before any device work.
+ * ldsp_sqbank_get_state copies out, per row, the mode, the timer and s after
+ * the last call; it waits for that call.
+ * Not built: a per-sample squelch, a per-row block or bandwidth, callbacks on
+ * rise, squelch inside ldsp_agc_execute_many, skipping closed rows inside
+ * FMBank / AudioBank, a noise-floor-tracking automatic threshold, in-place
+ * gating.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_sqbank_s *ldsp_sqbank_t;
+int ldsp_sqbank_create(unsigned int C, unsigned int B, double alpha, double threshold_dB, unsigned int timeout,
+                       ldsp_sqbank_t *q);
+int ldsp_sqbank_destroy(ldsp_sqbank_t q);
+int ldsp_sqbank_reset(ldsp_sqbank_t q);
+int ldsp_sqbank_set_thresholds(ldsp_sqbank_t q, const double *dB, unsigned int n);  /* n = 1 or C */
+/* Either pointer may be NULL; C values each: dB as set, lin as the kernel compares. */
+int ldsp_sqbank_get_thresholds(ldsp_sqbank_t q, double *dB, float *lin);
+/* Any pointer may be NULL.  fill: samples per row carried to the next call. */
+int ldsp_sqbank_get_info(ldsp_sqbank_t q, unsigned int *C, unsigned int *B, double *alpha, unsigned int *timeout,
+                         unsigned int *fill);
+int ldsp_sqbank_num_outputs(ldsp_sqbank_t q, size_t K, size_t *nblocks);
+int ldsp_sqbank_execute(ldsp_sqbank_t q, const void *x, size_t ldx, size_t K, uint8_t *status, size_t lds, float *level,
+                        size_t ldl, void *y, size_t ldy, size_t *nblocks, int mem, void *stream);
+/* Any pointer may be NULL; C values each. */
+int ldsp_sqbank_get_state(ldsp_sqbank_t q, int *mode, unsigned int *timer, double *s);
+/* Test hook: blocks per workgroup of the power kernel. */
+int ldsp_debug_sqbank_tile(unsigned int B, size_t *blocks);
 
 /* ------------------------------------------------------------------------
  * Spectrogram: a streaming Welch periodogram, one complex64 stream to rows of

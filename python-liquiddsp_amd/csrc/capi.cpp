@@ -1411,6 +1411,36 @@ struct ldsp_audiobank_s : ldsp::DevObj {
     }
 };
 
+// SquelchBank (per-row level and squelch gate over bank rows): the thresholds
+// in dB as set and as the float32 the kernel compares, the host-side stream
+// position (fill and the block count of a call follow from it), and on the
+// device the thresholds, per row the smoothed power, mode and timer (updated in
+// place by the one lane that owns the row), the carried samples of the
+// unfinished block as [C][B], ping-ponged, and the block powers of one call.
+struct ldsp_sqbank_s : ldsp::DevObj {
+    unsigned int C = 0, B = 0, timeout = 0;
+    double alpha = 0.0;
+    std::vector<double> thr_db;
+    std::vector<float> thr;
+    uint64_t seen = 0;                     // input samples per row since create / reset
+    ldsp::DevBuf dthr, dstate, dpow;
+    ldsp::PingPong hist;
+    ldsp::Staging stg_status, stg_level;   // the other two outputs of a host-memory call (stg: x and y)
+    size_t fill() const { return (size_t)(seen % B); }
+    size_t num_outputs(size_t K) const { return (size_t)((seen + K) / B - seen / B); }
+    static ldsp::k::SqState initial() { return {0.0, 1, 0}; }   // s = 0, ENABLED, timer 0
+    void zero_state(int dev)
+    {
+        ldsp::upload(dstate, std::vector<ldsp::k::SqState>(C, initial()), dev);
+        hist.zero((size_t)C * B * 8, dev);
+    }
+    void bind(int dev)
+    {
+        ldsp::upload(dthr, thr, dev);
+        zero_state(dev);
+    }
+};
+
 // Spectrogram (streaming Welch periodogram): the window, the host-side counts
 // (samples since reset, transforms since clear; the schedule follows from
 // them), and on the device the padded window, the twiddle table, the last
@@ -4141,6 +4171,169 @@ int ldsp_debug_audiobank_tile(ldsp_audiobank_t q, size_t* outputs)
         NONNULL(q);
         NONNULL(outputs);
         *outputs = (size_t)q->tile();
+    });
+}
+
+// ---------------------------------------------------------------- SquelchBank
+// thr = (float) 10^(dB / 10), the power in double
+static void sqbank_thresholds(const double* dB, unsigned int n, unsigned int C, std::vector<double>& db, std::vector<float>& lin)
+{
+    NONNULL(dB);
+    LDSP_REQUIRE(n == 1 || n == C, "sqbank: one threshold or one per row");
+    for (unsigned i = 0; i < n; i++) LDSP_REQUIRE(std::isfinite(dB[i]), "sqbank: thresholds must be finite");
+    db.resize(C);
+    lin.resize(C);
+    for (unsigned c = 0; c < C; c++) {
+        db[c] = dB[n == 1 ? 0 : c];
+        lin[c] = (float)pow(10.0, db[c] / 10.0);
+    }
+}
+int ldsp_sqbank_create(unsigned int C, unsigned int B, double alpha, double threshold_dB, unsigned int timeout,
+                       ldsp_sqbank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(C >= 1 && C <= (unsigned)k::kSqbankMaxC,
+                     "sqbank: the row count must lie in 1 .. " + std::to_string(k::kSqbankMaxC));
+        LDSP_REQUIRE(B >= (unsigned)k::kSqbankMinB && B <= (unsigned)k::kSqbankMaxB,
+                     "sqbank: the block length must lie in " + std::to_string(k::kSqbankMinB) + " .. " +
+                         std::to_string(k::kSqbankMaxB));
+        LDSP_REQUIRE(alpha > 0.0 && alpha <= 1.0, "sqbank: the bandwidth must lie in (0, 1]");
+        LDSP_REQUIRE(timeout >= 1 && timeout <= (unsigned)INT32_MAX, "sqbank: the timeout must be at least one block");
+        std::unique_ptr<ldsp_sqbank_s> o(new ldsp_sqbank_s());
+        o->C = C;
+        o->B = B;
+        o->alpha = alpha;
+        o->timeout = timeout;
+        sqbank_thresholds(&threshold_dB, 1, C, o->thr_db, o->thr);
+        *q = o.release();
+    });
+}
+int ldsp_sqbank_destroy(ldsp_sqbank_t q) { return guard([&] { destroy(q); }); }
+int ldsp_sqbank_reset(ldsp_sqbank_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        q->seen = 0;
+        q->at_rest([&] { q->zero_state(q->device); });
+    });
+}
+int ldsp_sqbank_set_thresholds(ldsp_sqbank_t q, const double* dB, unsigned int n)
+{
+    return guard([&] {
+        NONNULL(q);
+        std::vector<double> db;
+        std::vector<float> lin;
+        sqbank_thresholds(dB, n, q->C, db, lin);
+        // the table changes only once the object's earlier calls have finished with it
+        q->at_rest([&] { ldsp::upload(q->dthr, lin, q->device); });
+        q->thr_db = std::move(db);
+        q->thr = std::move(lin);
+    });
+}
+int ldsp_sqbank_get_thresholds(ldsp_sqbank_t q, double* dB, float* lin)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (dB) std::copy(q->thr_db.begin(), q->thr_db.end(), dB);
+        if (lin) std::copy(q->thr.begin(), q->thr.end(), lin);
+    });
+}
+int ldsp_sqbank_get_info(ldsp_sqbank_t q, unsigned int* C, unsigned int* B, double* alpha, unsigned int* timeout,
+                         unsigned int* fill)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (C) *C = q->C;
+        if (B) *B = q->B;
+        if (alpha) *alpha = q->alpha;
+        if (timeout) *timeout = q->timeout;
+        if (fill) *fill = (unsigned)q->fill();
+    });
+}
+int ldsp_sqbank_num_outputs(ldsp_sqbank_t q, size_t K, size_t* nblocks)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(nblocks);
+        *nblocks = q->num_outputs(K);
+    });
+}
+int ldsp_sqbank_execute(ldsp_sqbank_t q, const void* x, size_t ldx, size_t K, uint8_t* status, size_t lds, float* level,
+                        size_t ldl, void* y, size_t ldy, size_t* nblocks, int mem, void* stream)
+{
+    LDSP_RANGE("ldsp_sqbank_execute");
+    return guard([&] {
+        NONNULL(q);
+        const size_t N = q->num_outputs(K), B = q->B;
+        if (nblocks) *nblocks = N;
+        LDSP_REQUIRE(ldx >= K, "sqbank_execute: input row stride below the number of samples");
+        if (N > lds || N > ldl) throw Error(LDSP_ERANGE, "sqbank_execute: status or level row stride below the number of blocks");
+        if (y && N * B > ldy) throw Error(LDSP_ERANGE, "sqbank_execute: output row stride below the blocks' samples");
+        LDSP_REQUIRE(K == 0 || x, "sqbank_execute: NULL input");
+        LDSP_REQUIRE(N == 0 || (status && level), "sqbank_execute: NULL status or level");
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
+        const size_t C = q->C;
+        // a host-memory call reads and writes dense device images (rows of the caller's
+        // images are ldx, lds, ldl and ldy elements apart)
+        const void* dx = q->stg.dev_in(e, x, K * 8, C, ldx * 8);
+        uint8_t* dstat = (uint8_t*)q->stg_status.dev_out(e, status, C * N);
+        float* dlev = (float*)q->stg_level.dev_out(e, level, C * N * 4);
+        void* dy = y ? q->stg.dev_out(e, y, C * N * B * 8) : nullptr;
+        if (K > 0) {
+            k::SqbankCall c;
+            c.x = dx;
+            c.hist = q->hist.in();
+            c.hist_out = q->hist.out();
+            c.n = K;
+            c.ldx = e.host ? K : ldx;
+            c.fill = q->fill();
+            c.nblocks = N;
+            c.lds = e.host ? N : lds;
+            c.ldl = e.host ? N : ldl;
+            c.ldy = e.host ? N * B : ldy;
+            c.C = (int)C;
+            c.B = (int)B;
+            c.timeout = (int)q->timeout;
+            c.alpha = q->alpha;
+            c.thr = q->dthr.as<float>();
+            c.st = q->dstate.as<k::SqState>();
+            c.p = (double*)q->dpow.ensure(std::max<size_t>(C * N, 1) * 8, e.device);
+            c.status = dstat;
+            c.level = dlev;
+            c.y = dy;
+            k::sqbank(c, e.stream);
+            q->hist.flip();
+            q->seen += K;
+        }
+        call.end();
+        q->stg_status.finish(e, status, N, C, lds);
+        q->stg_level.finish(e, level, N * 4, C, ldl * 4);
+        if (y) q->stg.finish(e, y, N * B * 8, C, ldy * 8);
+    });
+}
+int ldsp_sqbank_get_state(ldsp_sqbank_t q, int* mode, unsigned int* timer, double* s)
+{
+    return guard([&] {
+        NONNULL(q);
+        std::vector<k::SqState> st(q->C, ldsp_sqbank_s::initial());
+        q->at_rest([&] { LDSP_HIP(hipMemcpy(st.data(), q->dstate.p, st.size() * sizeof(k::SqState), hipMemcpyDeviceToHost)); });
+        for (unsigned c = 0; c < q->C; c++) {
+            if (mode) mode[c] = st[c].mode;
+            if (timer) timer[c] = (unsigned)st[c].timer;
+            if (s) s[c] = st[c].s;
+        }
+    });
+}
+int ldsp_debug_sqbank_tile(unsigned int B, size_t* blocks)
+{
+    return guard([&] {
+        NONNULL(blocks);
+        LDSP_REQUIRE(B >= (unsigned)k::kSqbankMinB && B <= (unsigned)k::kSqbankMaxB,
+                     "sqbank: the block length must lie in " + std::to_string(k::kSqbankMinB) + " .. " +
+                         std::to_string(k::kSqbankMaxB));
+        *blocks = (size_t)k::sqbank_tile((int)B);
     });
 }
 

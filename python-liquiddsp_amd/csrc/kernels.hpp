@@ -497,6 +497,39 @@ struct AudiobankCall {
     void* y;
 };
 void audiobank(const AudiobankCall& c, hipStream_t s);
+// k_sqbank.hip: per-row level and squelch gate over bank rows (SquelchBank).
+// C <= kSqbankMaxC rows of complex64, row c's n samples at x + c * ldx; blocks of
+// kSqbankMinB <= B <= kSqbankMaxB samples.  The call's stream per row is the
+// fill < B carried samples (hist, [C][B]) followed by x; it holds nblocks =
+// (fill + n) / B whole blocks, and hist_out (a distinct buffer) receives the
+// (fill + n) mod B samples after them.  p: scratch for nblocks doubles per row.
+// st: per row the smoothed power, the mode and the timer, updated in place;
+// thr: per row the linear threshold.  level[c * ldl + b] and status[c * lds + b],
+// b < nblocks, receive row c; y (may be NULL: the gate is not launched) receives
+// nblocks B samples per row at y + c * ldy.  n = 0 launches nothing.
+constexpr int kSqbankMaxC = 256;
+constexpr int kSqbankMinB = 16;
+constexpr int kSqbankMaxB = 4096;
+int sqbank_tile(int B);                                     // blocks per workgroup of k_sqbank_power
+struct SqState {
+    double s;
+    int mode, timer;
+};
+struct SqbankCall {
+    const void* x;
+    const void* hist;
+    void* hist_out;
+    size_t n, ldx, fill, nblocks, lds, ldl, ldy;
+    int C, B, timeout;
+    double alpha;
+    const float* thr;
+    SqState* st;
+    double* p;
+    uint8_t* status;
+    float* level;
+    void* y;
+};
+void sqbank(const SqbankCall& c, hipStream_t s);
 // k_synth.hip: polyphase synthesis filter bank (Synthesizer), k_chan's
 // counterpart.  M rows (a power of two, 4 .. 256), interpolation D = M or M / 2,
 // Q = ceil(L / D) <= synth_qmax(M, D) taps per output residue.  y: row k at

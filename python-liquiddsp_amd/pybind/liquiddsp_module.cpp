@@ -94,13 +94,18 @@ T get_value(G get, const Q& q)
 }
 
 // The element kinds of inputs and results
-enum class Kind { f32, c64, i16 };
+enum class Kind { f32, c64, i16, u8 };
 constexpr Kind kind_of(bool cplx) { return cplx ? Kind::c64 : Kind::f32; }
-const char* torch_name(Kind k) { return k == Kind::c64 ? "complex64" : (k == Kind::f32 ? "float32" : "int16"); }
-size_t kind_size(Kind k) { return k == Kind::c64 ? 8 : (k == Kind::f32 ? 4 : 2); }
+const char* torch_name(Kind k)
+{
+    return k == Kind::c64 ? "complex64" : (k == Kind::f32 ? "float32" : (k == Kind::i16 ? "int16" : "uint8"));
+}
+size_t kind_size(Kind k) { return k == Kind::c64 ? 8 : (k == Kind::f32 ? 4 : (k == Kind::i16 ? 2 : 1)); }
 py::dtype np_dtype(Kind k)
 {
-    return k == Kind::c64 ? py::dtype::of<cf>() : (k == Kind::f32 ? py::dtype::of<float>() : py::dtype::of<int16_t>());
+    return k == Kind::c64 ? py::dtype::of<cf>()
+                          : (k == Kind::f32 ? py::dtype::of<float>()
+                                            : (k == Kind::i16 ? py::dtype::of<int16_t>() : py::dtype::of<uint8_t>()));
 }
 // The dtype dispatch of Delay and HilbertTransform: complex64 or float32, false for anything else
 bool kind_from_dtype(const py::handle& x, Kind* k)
@@ -1168,6 +1173,95 @@ struct FMBank {
     }
 };
 
+// ------------------------------------------------------------------ SquelchBank (liquid: the squelch half of agc_crcf per row, per block)
+// Input as the FMBank's.  Each call returns new arrays where its input is;
+// status and level keep the last call's.
+struct SquelchBank {
+    Handle<ldsp_sqbank_t, ldsp_sqbank_destroy> q;
+    unsigned C = 0, B = 0, tmo = 0;
+    double alpha = 0.0;
+    py::object last_status = py::none(), last_level = py::none();
+    static std::vector<double> to_dvec(const py::object& o)
+    {
+        auto a = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(o);
+        if (!a) throw py::error_already_set();
+        return std::vector<double>(a.data(), a.data() + a.size());
+    }
+    SquelchBank(int nchan, int block, const py::object& threshold, double bandwidth, int timeout)
+    {
+        if (nchan < 0) throw py::value_error("SquelchBank: nchan must lie in 1 .. 256");
+        if (block < 0) throw py::value_error("SquelchBank: block must lie in 16 .. 4096");
+        if (timeout < 0) throw py::value_error("SquelchBank: timeout must be >= 1");
+        const std::vector<double> t = to_dvec(threshold);
+        if (t.empty()) throw py::value_error("SquelchBank: one threshold or one per row");
+        check(ldsp_sqbank_create((unsigned)nchan, (unsigned)block, bandwidth, t[0], (unsigned)timeout, q.out()));
+        check(ldsp_sqbank_get_info(q, &C, &B, &alpha, &tmo, nullptr));
+        if (t.size() > 1) check(ldsp_sqbank_set_thresholds(q, t.data(), (unsigned)t.size()));
+    }
+    void reset() { check(ldsp_sqbank_reset(q)); }
+    py::array_t<double> get_threshold()
+    {
+        py::array_t<double> t(C);
+        check(ldsp_sqbank_get_thresholds(q, t.mutable_data(), nullptr));
+        return t;
+    }
+    void set_threshold(const py::object& o)
+    {
+        const std::vector<double> t = to_dvec(o);
+        check(ldsp_sqbank_set_thresholds(q, t.data(), (unsigned)t.size()));
+    }
+    py::array_t<float> threshold_linear()
+    {
+        py::array_t<float> t(C);
+        check(ldsp_sqbank_get_thresholds(q, nullptr, t.mutable_data()));
+        return t;
+    }
+    unsigned fill()
+    {
+        unsigned f;
+        check(ldsp_sqbank_get_info(q, nullptr, nullptr, nullptr, nullptr, &f));
+        return f;
+    }
+    size_t tile()
+    {
+        size_t t;
+        check(ldsp_debug_sqbank_tile(B, &t));
+        return t;
+    }
+    size_t num_outputs(size_t K)
+    {
+        size_t n;
+        check(ldsp_sqbank_num_outputs(q, K, &n));
+        return n;
+    }
+    py::tuple state()
+    {
+        py::array_t<int> mode(C);
+        py::array_t<unsigned> timer(C);
+        py::array_t<double> s(C);
+        check(ldsp_sqbank_get_state(q, mode.mutable_data(), timer.mutable_data(), s.mutable_data()));
+        return py::make_tuple(mode, timer, s);
+    }
+    // status, level and (gate) the gated rows of the call's whole blocks
+    py::object run(const py::handle& x, bool gate)
+    {
+        const CallIn in = in_rows(x, Kind::c64, C, "SquelchBank", true, Strided::refuse);
+        size_t N = 0, nw = 0;
+        check(ldsp_sqbank_num_outputs(q, in.n, &N));
+        CallOut st = make_out(in, Kind::u8, C, (py::ssize_t)N), lv = make_out(in, Kind::f32, C, (py::ssize_t)N), y;
+        if (gate) y = make_out(in, Kind::c64, C, (py::ssize_t)(N * B));
+        invoke(in, [&](int mem, void* s) {
+            return ldsp_sqbank_execute(q, in.ptr, in.ld, in.n, (uint8_t*)st.ptr, N, (float*)lv.ptr, N, y.ptr, N * B, &nw,
+                                       mem, s);
+        });
+        last_status = st.obj;
+        last_level = lv.obj;
+        return gate ? y.obj : py::object(py::make_tuple(st.obj, lv.obj));
+    }
+    py::object call(const py::handle& x) { return run(x, true); }
+    py::object measure(const py::handle& x) { return run(x, false); }
+};
+
 // ------------------------------------------------------------------ AudioBank (liquid: iirfilt_rrrf + resamp_rrrf per row)
 // De-emphasis and arbitrary-rate resampler over bank rows (ldsp.h): float32[nchan, K]
 // -> float32[nchan, nout] (int16 with pcm16).  A device tensor whose columns are
@@ -1978,6 +2072,33 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def_property_readonly("skip", &FMBank::skip, "input samples per row before the next call's first output")
         .def_property_readonly("tile", &FMBank::tile, "output columns per workgroup of the kernel")
         .def("__call__", &FMBank::call, "complex64[nchan, K] -> float32[nchan, ncols]");
+
+    // ---- SquelchBank (beyond the reference: per-row level and squelch gate over bank rows)
+    py::class_<SquelchBank>(m, "SquelchBank")
+        .def(py::init<int, int, py::object, double, int>(), py::arg("nchan"), py::arg("block") = 1024,
+             py::arg("threshold") = -30.0, py::arg("bandwidth") = 0.25, py::arg("timeout") = 4)
+        .def("reset", &SquelchBank::reset, "the initial state; the thresholds stay")
+        .def("num_outputs", &SquelchBank::num_outputs, py::arg("K"),
+             "blocks the next call returns for K input samples per row")
+        .def_property_readonly("nchan", [](SquelchBank& c) { return c.C; })
+        .def_property_readonly("block", [](SquelchBank& c) { return c.B; })
+        .def_property_readonly("bandwidth", [](SquelchBank& c) { return c.alpha; })
+        .def_property_readonly("timeout", [](SquelchBank& c) { return c.tmo; }, "in blocks")
+        .def_property("threshold", &SquelchBank::get_threshold, &SquelchBank::set_threshold,
+                      "dB per row; set with a scalar or nchan values, from the next block on")
+        .def_property_readonly("threshold_linear", &SquelchBank::threshold_linear,
+                               "the float32 values the level is compared with")
+        .def_property_readonly("fill", &SquelchBank::fill, "samples per row carried to the next call")
+        .def_property_readonly("tile", &SquelchBank::tile, "blocks per workgroup of the power kernel")
+        .def_property_readonly("status", [](SquelchBank& c) { return c.last_status; },
+                               "the last call's uint8[nchan, nblocks], liquid's squelch codes; None before the first")
+        .def_property_readonly("level", [](SquelchBank& c) { return c.last_level; },
+                               "the last call's float32[nchan, nblocks], linear power; None before the first")
+        .def_property_readonly("state", &SquelchBank::state, "(mode, timer, smoothed power) per row after the last call")
+        .def("measure", &SquelchBank::measure, py::arg("x"),
+             "complex64[nchan, K] -> (status, level); advances the stream, writes no rows")
+        .def("__call__", &SquelchBank::call,
+             "complex64[nchan, K] -> complex64[nchan, nblocks * block]: the stream's whole blocks, closed ones zeroed");
 
     // ---- AudioBank (beyond the reference: de-emphasis and resampler over bank rows)
     py::class_<AudioBank>(m, "AudioBank")
