@@ -854,6 +854,94 @@ int ldsp_sqbank_get_state(ldsp_sqbank_t q, int *mode, unsigned int *timer, doubl
 int ldsp_debug_sqbank_tile(unsigned int B, size_t *blocks);
 
 /* ------------------------------------------------------------------------
+ * StereoBank: for every row of a float32 [C][K] block of FM multiplex (MPX)
+ * samples (the output of an FMBank(C, kf, 1), read in place), a feed-forward FM
+ * stereo decoder: the mono sum, the 38 kHz difference and the 19 kHz pilot by
+ * three decimating FIRs over one read of the row, and left and right from
+ * them, in one launch for all rows.  The reference's FMStereo (one stream, a
+ * per-sample pilot PLL) is a different decoder and stays as it is; the
+ * definition here is this library's own.  For row c of the concatenated input
+ * u[c][t] (t counted from 0 since creation or reset, u = 0 before t = 0), the
+ * 32-bit pilot word w = rint(pilot 2^32) mod 2^32 (pilot in cycles per sample,
+ * 19 kHz / fs; the product is exact, ties go to even), a decimation D, two real
+ * prototypes of the same length L, h for the audio and g for the pilot, and a
+ * pilot threshold thr:
+ *   s[c][n] = sum_{j<L} h[j] u[c][nD-j]
+ *   z[c][n] = sum_{j<L} h[j] u[c][nD-j] exp(-2 pi i (((nD-j) * 2w) mod 2^32) / 2^32)
+ *   P[c][n] = sum_{j<L} g[j] u[c][nD-j] exp(-2 pi i (((nD-j) *  w) mod 2^32) / 2^32)
+ *   m       = |P|^2                         (float32, on the value the kernel holds)
+ *   S       = m > thr^2 ? 2 Im(z conj(P)^2) / m : 0          (thr^2 = thr * thr in float32)
+ *   left[c][n] = s + S ,  right[c][n] = s - S
+ * For the standard multiplex 0.45 (l + r) + 0.45 (l - r) sin 2 theta +
+ * a_p sin theta this gives left = 0.9 l and right = 0.9 r delayed by (L - 1) / 2
+ * input samples: conj(P)^2 / |P|^2 carries the pilot's doubled phase, whatever
+ * its offset from the nominal frequency is inside g's pass band, so nothing is
+ * tracked from column to column and a row has no serial state but its last
+ * L - 1 raw samples.  Below the threshold the row is mono: left = right = s,
+ * the same bits.
+ * The sums are evaluated with the complex taps
+ *   gz[j] = h[j] exp(+2 pi i ((j 2w) mod 2^32) / 2^32)          (double, rounded once)
+ *   gp[j] = g[j] exp(+2 pi i ((j  w) mod 2^32) / 2^32)
+ *   z' = sum_j gz[j] u[c][nD-j],   P' = sum_j gp[j] u[c][nD-j]
+ * The phase is additive modulo 2^32, so z = rz z' and P = rp P' with
+ * rp = exp(-2 pi i ((nD w) mod 2^32) / 2^32) and rz likewise with 2w; and
+ * (nD 2w) mod 2^32 = 2 ((nD w) mod 2^32) mod 2^32, so rz = rp^2 exactly,
+ * z conj(P)^2 = z' conj(P')^2 and |P| = |P'|: neither m nor S depends on the
+ * per-output rotations, and they are not applied.  No step depends on the
+ * stream position beyond skip, so the result is exact for any stream length.
+ * Every row of left and right is within 1e-6 of the float64 evaluation of the
+ * definition (max-norm, relative to the row's maximum) for a pilot of
+ * amplitude 0.1; a weaker pilot divides the same absolute error by a smaller m.
+ * The column schedule is the Channelizer's and the FMBank's: output n is
+ * emitted by the call that delivers sample nD of every row; with T samples per
+ * row seen before a call and skip = (-T) mod D, a call of K samples per row
+ * returns K > skip ? ceil((K - skip) / D) : 0 columns; calls of any K, 0
+ * included, are allowed.  A row's bits depend neither on how the stream is cut
+ * into calls, nor on the other rows, their number or order, nor on the row
+ * strides.
+ *   1 <= C <= 128, fixed at creation (the 2 C output rows fit an AudioBank);
+ *   1 <= D <= 32;  1 <= L <= 1025;  0 < pilot < 0.25;  thr >= 0;  as > 0.
+ * ldsp_stbank_create designs, with L = 0 standing for 2 ceil(8.5 / pilot) + 1,
+ *   h = firdes_kaiser(L, (float)((17/19) pilot), as, 0),
+ *   g = firdes_kaiser(L, (float)(( 2/19) pilot), as, 0),
+ * each tap then divided in double by the double sum of the float32 design and
+ * rounded once (unit DC gain).  ldsp_stbank_create_taps takes h and g as given;
+ * they must have the same length.  A value out of range (a NaN among them), a
+ * NULL pointer and prototypes of unequal length are LDSP_EINVAL; a default L
+ * above 1025 (pilot below about 0.0166) is LDSP_EUNSUP.
+ * ldsp_stbank_set_threshold takes effect at the next call and touches no state.
+ * ldsp_stbank_execute reads row c at x + c * ldx and writes left of row c to
+ * y + (2 c) * ldy and right to y + (2 c + 1) * ldy (all in samples, ldx >= K):
+ * the output is a [2 C][ncols] image an AudioBank(2 C, ...) reads in place.  It
+ * sets *ncols and, when ldy < *ncols, returns LDSP_ERANGE without consuming the
+ * input.  Argument errors are decided on the host before any device work.
+ * ldsp_stbank_get_pilot_level copies out, per row, sqrtf(m) of the last column
+ * emitted (0 before any); it waits for the last call.
+ * Not built: smoothing of P across columns, a stereo blend, RDS, a per-row
+ * pilot or threshold, any change of the reference-parity FMStereo.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_stbank_s *ldsp_stbank_t;
+/* L = 0: the default length. */
+int ldsp_stbank_create(unsigned int C, double pilot, unsigned int D, unsigned int L, float as, float threshold,
+                       ldsp_stbank_t *q);
+int ldsp_stbank_create_taps(unsigned int C, double pilot, unsigned int D, const float *h, unsigned int L,
+                            const float *g, unsigned int Lg, float threshold, ldsp_stbank_t *q);
+int ldsp_stbank_destroy(ldsp_stbank_t q);
+int ldsp_stbank_reset(ldsp_stbank_t q);
+/* Any pointer may be NULL.  skip: input samples per row before the next call's first output; w: the pilot word. */
+int ldsp_stbank_get_info(ldsp_stbank_t q, unsigned int *C, unsigned int *D, unsigned int *L, unsigned int *skip,
+                         uint32_t *w);
+int ldsp_stbank_get_taps(ldsp_stbank_t q, float *h, float *g);   /* L floats each; either may be NULL */
+int ldsp_stbank_get_threshold(ldsp_stbank_t q, float *thr);
+int ldsp_stbank_set_threshold(ldsp_stbank_t q, float thr);
+int ldsp_stbank_num_outputs(ldsp_stbank_t q, size_t K, size_t *ncols);
+int ldsp_stbank_execute(ldsp_stbank_t q, const void *x, size_t ldx, size_t K, void *y, size_t ldy, size_t *ncols,
+                        int mem, void *stream);
+int ldsp_stbank_get_pilot_level(ldsp_stbank_t q, float *level);  /* C floats */
+/* Test hook: output columns per workgroup of the (D, L) kernel. */
+int ldsp_debug_stbank_tile(unsigned int D, unsigned int L, size_t *frames);
+
+/* ------------------------------------------------------------------------
  * Spectrogram: a streaming Welch periodogram, one complex64 stream to rows of
  * power per bin and a running mean of them.  No reference counterpart
  * (liquid's spgramcf / spwaterfallcf are the same block: a zeroed window

@@ -1441,6 +1441,48 @@ struct ldsp_sqbank_s : ldsp::DevObj {
     }
 };
 
+// StereoBank (FM stereo decoder over bank rows): the two prototypes, the pilot
+// word and threshold, the host-side stream position (skip follows from it), and
+// on the device the tap table in the kernel's layout (kernels.hpp), per row the
+// last L - 1 raw samples, ping-ponged, and per row the pilot level of the last
+// column emitted.  The history is raw input, so a new threshold touches no state.
+struct ldsp_stbank_s : ldsp::DevObj, Decimating<ldsp_stbank_s> {
+    unsigned int C = 0, D = 1;
+    uint32_t w = 0;
+    float thr = 0.0f;
+    std::vector<float> h, g;               // audio and pilot prototypes, the same length
+    uint64_t seen = 0;                     // input samples per row since create / reset
+    ldsp::DevBuf dtaps, dlevel;
+    ldsp::PingPong hist;
+    size_t hist_bytes() const { return std::max<size_t>((size_t)C * (h.size() - 1), 1) * 4; }
+    void zero_state(int dev)
+    {
+        hist.zero(hist_bytes(), dev);
+        ldsp::zero_now(dlevel.ensure((size_t)C * 4, dev), 0, (size_t)C * 4);
+    }
+    // gz[j] = h[j] exp(+2 pi i ((j 2w) mod 2^32) / 2^32), gp[j] = g[j] exp(+2 pi i ((j w) mod 2^32) / 2^32)
+    // in double, rounded once; the phase as a signed count of 2^-31 half-turns
+    void bind(int dev)
+    {
+        const size_t L = h.size();
+        std::vector<float> t(8 * L, 0.0f);
+        for (size_t j = 0; j < L; j++) {
+            const double az = M_PI * ((double)(int32_t)((uint32_t)j * (2u * w)) / 2147483648.0);
+            const double ap = M_PI * ((double)(int32_t)((uint32_t)j * w) / 2147483648.0);
+            float* e = &t[8 * (L - 1 - j)];
+            e[0] = h[j];
+            e[1] = (float)((double)h[j] * cos(az));
+            e[2] = (float)((double)h[j] * sin(az));
+            e[3] = (float)((double)g[j] * cos(ap));
+            e[4] = (float)((double)g[j] * sin(ap));
+            const int slot = ldsp::k::stbank_slot((int)D, (int)L, (int)(L - 1 - j));
+            std::memcpy(&e[5], &slot, 4);
+        }
+        ldsp::upload(dtaps, t, dev);
+        zero_state(dev);
+    }
+};
+
 // Spectrogram (streaming Welch periodogram): the window, the host-side counts
 // (samples since reset, transforms since clear; the schedule follows from
 // them), and on the device the padded window, the twiddle table, the last
@@ -4334,6 +4376,186 @@ int ldsp_debug_sqbank_tile(unsigned int B, size_t* blocks)
                      "sqbank: the block length must lie in " + std::to_string(k::kSqbankMinB) + " .. " +
                          std::to_string(k::kSqbankMaxB));
         *blocks = (size_t)k::sqbank_tile((int)B);
+    });
+}
+
+// ---------------------------------------------------------------- StereoBank
+// w = rint(pilot 2^32): the product is exact (a power of two), rint rounds ties to even; 0 < pilot < 0.25 keeps it below 2^30
+static uint32_t stbank_check_shape(unsigned int C, double pilot, unsigned int D, float thr)
+{
+    LDSP_REQUIRE(C >= 1 && C <= (unsigned)k::kStbankMaxC,
+                 "stbank: the row count must lie in 1 .. " + std::to_string(k::kStbankMaxC));
+    LDSP_REQUIRE(pilot > 0.0 && pilot < 0.25, "stbank: the pilot frequency must lie in (0, 0.25) cycles per sample");
+    LDSP_REQUIRE(D >= 1 && D <= (unsigned)k::kStbankMaxD,
+                 "stbank: the decimation must lie in 1 .. " + std::to_string(k::kStbankMaxD));
+    LDSP_REQUIRE(thr >= 0.0f, "stbank: the pilot threshold must be >= 0");
+    return (uint32_t)(uint64_t)std::nearbyint(pilot * 4294967296.0);
+}
+static void stbank_check_length(unsigned int L)
+{
+    LDSP_REQUIRE(L >= 1 && L <= (unsigned)k::kStbankMaxL,
+                 "stbank: the prototype length must lie in 1 .. " + std::to_string(k::kStbankMaxL));
+}
+static ldsp_stbank_s* stbank_make(unsigned int C, uint32_t w, unsigned int D, float thr, std::vector<float> h,
+                                  std::vector<float> g)
+{
+    std::unique_ptr<ldsp_stbank_s> o(new ldsp_stbank_s());
+    o->C = C;
+    o->D = D;
+    o->w = w;
+    o->thr = thr;
+    o->h = std::move(h);
+    o->g = std::move(g);
+    return o.release();
+}
+// firdes_kaiser(L, fc, as, 0) with every tap divided in double by the double sum of the float32 design, rounded once
+static std::vector<float> stbank_design(unsigned int L, double fc, float as)
+{
+    std::vector<float> h = design::firdes_kaiser(L, (float)fc, as, 0.0f);
+    double sum = 0.0;
+    for (float v : h) sum += (double)v;
+    for (float& v : h) v = (float)((double)v / sum);
+    return h;
+}
+int ldsp_stbank_create(unsigned int C, double pilot, unsigned int D, unsigned int L, float as, float threshold,
+                       ldsp_stbank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        const uint32_t w = stbank_check_shape(C, pilot, D, threshold);
+        LDSP_REQUIRE(as > 0.0f, "stbank: stop-band attenuation must be > 0");
+        if (L == 0) {                                 // the default length
+            const double half = std::ceil(8.5 / pilot);
+            if (2.0 * half + 1.0 > (double)k::kStbankMaxL)
+                throw Error(LDSP_EUNSUP, "stbank: a default prototype above " + std::to_string(k::kStbankMaxL) +
+                                             " taps is not implemented (pilot too low)");
+            L = 2 * (unsigned)half + 1;
+        }
+        stbank_check_length(L);
+        *q = stbank_make(C, w, D, threshold, stbank_design(L, 17.0 / 19.0 * pilot, as),
+                         stbank_design(L, 2.0 / 19.0 * pilot, as));
+    });
+}
+int ldsp_stbank_create_taps(unsigned int C, double pilot, unsigned int D, const float* h, unsigned int L, const float* g,
+                            unsigned int Lg, float threshold, ldsp_stbank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        const uint32_t w = stbank_check_shape(C, pilot, D, threshold);
+        stbank_check_length(L);
+        LDSP_REQUIRE(Lg == L, "stbank: the audio and the pilot prototype must have the same length");
+        NONNULL(h);
+        NONNULL(g);
+        *q = stbank_make(C, w, D, threshold, std::vector<float>(h, h + L), std::vector<float>(g, g + L));
+    });
+}
+int ldsp_stbank_destroy(ldsp_stbank_t q) { return guard([&] { destroy(q); }); }
+int ldsp_stbank_reset(ldsp_stbank_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        q->seen = 0;
+        q->at_rest([&] { q->zero_state(q->device); });
+    });
+}
+int ldsp_stbank_get_info(ldsp_stbank_t q, unsigned int* C, unsigned int* D, unsigned int* L, unsigned int* skip,
+                         uint32_t* w)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (C) *C = q->C;
+        if (D) *D = q->D;
+        if (L) *L = (unsigned)q->h.size();
+        if (skip) *skip = (unsigned)q->skip();
+        if (w) *w = q->w;
+    });
+}
+int ldsp_stbank_get_taps(ldsp_stbank_t q, float* h, float* g)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (h) std::copy(q->h.begin(), q->h.end(), h);
+        if (g) std::copy(q->g.begin(), q->g.end(), g);
+    });
+}
+int ldsp_stbank_get_threshold(ldsp_stbank_t q, float* t) { return guard([&] { NONNULL(q); NONNULL(t); *t = q->thr; }); }
+int ldsp_stbank_set_threshold(ldsp_stbank_t q, float t)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(t >= 0.0f, "stbank: the pilot threshold must be >= 0");
+        q->thr = t;                                   // a kernel argument of the next call
+    });
+}
+int ldsp_stbank_num_outputs(ldsp_stbank_t q, size_t K, size_t* ncols)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(ncols);
+        *ncols = q->num_outputs(K);
+    });
+}
+int ldsp_stbank_execute(ldsp_stbank_t q, const void* x, size_t ldx, size_t K, void* y, size_t ldy, size_t* ncols, int mem,
+                        void* stream)
+{
+    LDSP_RANGE("ldsp_stbank_execute");
+    return guard([&] {
+        NONNULL(q);
+        const size_t N = q->num_outputs(K);
+        if (ncols) *ncols = N;
+        LDSP_REQUIRE(ldx >= K, "stbank_execute: input row stride below the number of samples");
+        if (N > ldy) throw Error(LDSP_ERANGE, "stbank_execute: output row stride below the number of output columns");
+        LDSP_REQUIRE(K == 0 || x, "stbank_execute: NULL input");
+        LDSP_REQUIRE(N == 0 || y, "stbank_execute: NULL output");
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
+        const size_t C = q->C;
+        // a host-memory call reads and writes dense [C][K] and [2 C][N] device images
+        // (rows of the caller's images are ldx and ldy samples apart)
+        const void* dx = q->stg.dev_in(e, x, K * 4, C, ldx * 4);
+        float* dy = (float*)q->stg.dev_out(e, y, 2 * C * N * 4);
+        if (K > 0) {
+            k::StbankCall c;
+            c.x = (const float*)dx;
+            c.hist = (const float*)q->hist.in();
+            c.hist_out = (float*)q->hist.out();
+            c.n = K;
+            c.ldx = e.host ? K : ldx;
+            c.skip = q->skip();
+            c.ncols = N;
+            c.ldy = e.host ? N : ldy;
+            c.C = (int)C;
+            c.D = (int)q->D;
+            c.L = (int)q->h.size();
+            c.taps = q->dtaps.as<float>();
+            c.thr2 = q->thr * q->thr;
+            c.y = dy;
+            c.level = q->dlevel.as<float>();
+            k::stbank(c, e.stream);
+            q->hist.flip();
+            q->seen += K;
+        }
+        call.end();
+        q->stg.finish(e, y, N * 4, 2 * C, ldy * 4);
+    });
+}
+int ldsp_stbank_get_pilot_level(ldsp_stbank_t q, float* level)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(level);
+        std::fill(level, level + q->C, 0.0f);         // before the first call: nothing on the device yet
+        q->at_rest([&] { LDSP_HIP(hipMemcpy(level, q->dlevel.p, (size_t)q->C * 4, hipMemcpyDeviceToHost)); });
+    });
+}
+int ldsp_debug_stbank_tile(unsigned int D, unsigned int L, size_t* frames)
+{
+    return guard([&] {
+        NONNULL(frames);
+        LDSP_REQUIRE(D >= 1 && D <= (unsigned)k::kStbankMaxD,
+                     "stbank: the decimation must lie in 1 .. " + std::to_string(k::kStbankMaxD));
+        stbank_check_length(L);
+        *frames = (size_t)k::stbank_frames((int)D, (int)L);
     });
 }
 

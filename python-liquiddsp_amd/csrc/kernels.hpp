@@ -530,6 +530,35 @@ struct SqbankCall {
     void* y;
 };
 void sqbank(const SqbankCall& c, hipStream_t s);
+// k_stbank.hip: FM stereo decoder over bank rows (StereoBank).  C <= kStbankMaxC
+// rows of float32 multiplex, row c's n samples at x + c * ldx; decimation
+// 1 <= D <= kStbankMaxD, two real prototypes of L <= kStbankMaxL taps.  hist /
+// hist_out: per row the L - 1 raw samples before x[c][0] / before the next
+// call's first, [C][L - 1], distinct buffers (at least one readable sample when
+// L = 1).  The call's columns are at sample skip + m D, m < ncols, as k_chan's.
+// taps: the host's table [L][8] indexed by k = L - 1 - j: h[j], Re gz[j],
+// Im gz[j], Re gp[j], Im gp[j] (gz, gp: the complex taps of ldsp.h), the bits of
+// stbank_slot(D, L, k) and two words of padding.  thr2: the float32 square of
+// the pilot threshold.  y[(2 c) * ldy + m] receives row c's left,
+// y[(2 c + 1) * ldy + m] its right; level[c] receives sqrtf(|P|^2) of the call's
+// last column (untouched by a call without columns).  n = 0 launches nothing.
+constexpr int kStbankMaxC = 128;
+constexpr int kStbankMaxD = 32;
+constexpr int kStbankMaxL = 1025;
+int stbank_frames(int D, int L);                            // output columns per workgroup
+int stbank_slot(int D, int L, int k);                       // where the staged span keeps offset k of column 0
+struct StbankCall {
+    const float* x;
+    const float* hist;
+    float* hist_out;
+    size_t n, ldx, skip, ncols, ldy;
+    int C, D, L;
+    const float* taps;
+    float thr2;
+    float* y;
+    float* level;
+};
+void stbank(const StbankCall& c, hipStream_t s);
 // k_synth.hip: polyphase synthesis filter bank (Synthesizer), k_chan's
 // counterpart.  M rows (a power of two, 4 .. 256), interpolation D = M or M / 2,
 // Q = ceil(L / D) <= synth_qmax(M, D) taps per output residue.  y: row k at

@@ -1262,6 +1262,89 @@ struct SquelchBank {
     py::object measure(const py::handle& x) { return run(x, false); }
 };
 
+// ------------------------------------------------------------------ StereoBank (no reference counterpart; FMStereo is another decoder)
+// Feed-forward FM stereo decoder over bank rows (ldsp.h): float32[nchan, K] of
+// multiplex -> float32[nchan, 2, ncols], left at [:, 0] and right at [:, 1]; its
+// [2 nchan, ncols] view is an AudioBank's input.  Input as the AudioBank's: an
+// FMBank output, a block of rows or a range of columns of one is read in place.
+struct StereoBank {
+    Handle<ldsp_stbank_t, ldsp_stbank_destroy> q;
+    unsigned C = 0, D = 0, L = 0;
+    uint32_t w = 0;
+    StereoBank(int nchan, double pilot, int decim, const py::object& ntaps, float as, float thr, const py::object& taps,
+               const py::object& ptaps)
+    {
+        if (nchan < 0) throw py::value_error("StereoBank: nchan must lie in 1 .. 128");
+        if (decim < 0) throw py::value_error("StereoBank: decim must lie in 1 .. 32");
+        if (taps.is_none() != ptaps.is_none())
+            throw py::value_error("StereoBank: taps and pilot_taps come together");
+        if (!taps.is_none()) {
+            if (!ntaps.is_none()) throw py::value_error("StereoBank: ntaps or taps, not both");
+            std::vector<float> h = to_fvec(taps), g = to_fvec(ptaps);
+            check(ldsp_stbank_create_taps((unsigned)nchan, pilot, (unsigned)decim, h.data(), (unsigned)h.size(), g.data(),
+                                          (unsigned)g.size(), thr, q.out()));
+        } else {
+            const long n = ntaps.is_none() ? 0 : ntaps.cast<long>();
+            if (!ntaps.is_none() && (n < 1 || n > 1025)) throw py::value_error("StereoBank: ntaps must lie in 1 .. 1025");
+            check(ldsp_stbank_create((unsigned)nchan, pilot, (unsigned)decim, (unsigned)n, as, thr, q.out()));
+        }
+        check(ldsp_stbank_get_info(q, &C, &D, &L, nullptr, &w));
+    }
+    void reset() { check(ldsp_stbank_reset(q)); }
+    py::array_t<float> taps()
+    {
+        py::array_t<float> h(L);
+        check(ldsp_stbank_get_taps(q, h.mutable_data(), nullptr));
+        return h;
+    }
+    py::array_t<float> pilot_taps()
+    {
+        py::array_t<float> g(L);
+        check(ldsp_stbank_get_taps(q, nullptr, g.mutable_data()));
+        return g;
+    }
+    float get_threshold() { return get_value<float>(ldsp_stbank_get_threshold, q); }
+    void set_threshold(float t) { check(ldsp_stbank_set_threshold(q, t)); }
+    unsigned skip()
+    {
+        unsigned s;
+        check(ldsp_stbank_get_info(q, nullptr, nullptr, nullptr, &s, nullptr));
+        return s;
+    }
+    size_t tile()
+    {
+        size_t f = 0;
+        check(ldsp_debug_stbank_tile(D, L, &f));
+        return f;
+    }
+    size_t num_outputs(size_t K)
+    {
+        size_t c = 0;
+        check(ldsp_stbank_num_outputs(q, K, &c));
+        return c;
+    }
+    py::array_t<float> pilot_level()
+    {
+        py::array_t<float> v(C);
+        check(ldsp_stbank_get_pilot_level(q, v.mutable_data()));
+        return v;
+    }
+    py::array_t<bool> stereo()
+    {
+        const py::array_t<float> v = pilot_level();
+        const float t = get_threshold();
+        py::array_t<bool> s(C);
+        for (unsigned c = 0; c < C; c++) s.mutable_at(c) = v.at(c) > t;
+        return s;
+    }
+    py::object call(const py::handle& x)
+    {
+        py::object y = run_from_rows(q.get(), in_rows(x, Kind::f32, C, "StereoBank", true, Strided::refuse), Kind::f32,
+                                     2 * (py::ssize_t)C, ldsp_stbank_num_outputs, ldsp_stbank_execute);
+        return y.attr("reshape")(py::make_tuple(C, 2, y.attr("shape").attr("__getitem__")(1)));
+    }
+};
+
 // ------------------------------------------------------------------ AudioBank (liquid: iirfilt_rrrf + resamp_rrrf per row)
 // De-emphasis and arbitrary-rate resampler over bank rows (ldsp.h): float32[nchan, K]
 // -> float32[nchan, nout] (int16 with pcm16).  A device tensor whose columns are
@@ -2099,6 +2182,30 @@ PYBIND11_MODULE(_liquiddsp, m)
              "complex64[nchan, K] -> (status, level); advances the stream, writes no rows")
         .def("__call__", &SquelchBank::call,
              "complex64[nchan, K] -> complex64[nchan, nblocks * block]: the stream's whole blocks, closed ones zeroed");
+
+    // ---- StereoBank (beyond the reference: feed-forward FM stereo decoder over bank rows)
+    py::class_<StereoBank>(m, "StereoBank")
+        .def(py::init<int, double, int, py::object, float, float, py::object, py::object>(), py::arg("nchan"),
+             py::arg("pilot"), py::arg("decim") = 1, py::arg("ntaps") = py::none(), py::arg("As") = 60.0f,
+             py::arg("threshold") = 0.01f, py::arg("taps") = py::none(), py::arg("pilot_taps") = py::none())
+        .def("reset", &StereoBank::reset)
+        .def("num_outputs", &StereoBank::num_outputs, py::arg("K"),
+             "columns the next call returns for K input samples per row")
+        .def_property_readonly("nchan", [](StereoBank& c) { return c.C; })
+        .def_property_readonly("decim", [](StereoBank& c) { return c.D; })
+        .def_property_readonly("pilot", [](StereoBank& c) { return (double)c.w / 4294967296.0; },
+                               "the pilot word / 2**32, cycles per sample")
+        .def_property_readonly("word", [](StereoBank& c) { return c.w; }, "the 32-bit pilot word")
+        .def_property_readonly("taps", &StereoBank::taps, "the audio prototype")
+        .def_property_readonly("pilot_taps", &StereoBank::pilot_taps, "the pilot prototype")
+        .def_property("threshold", &StereoBank::get_threshold, &StereoBank::set_threshold,
+                      "pilot amplitude |P| above which a column is decoded in stereo; set from the next call on")
+        .def_property_readonly("skip", &StereoBank::skip, "input samples per row before the next call's first output")
+        .def_property_readonly("tile", &StereoBank::tile, "output columns per workgroup of the kernel")
+        .def_property_readonly("pilot_level", &StereoBank::pilot_level,
+                               "float32[nchan]: |P| of the last column emitted per row, 0 before any")
+        .def_property_readonly("stereo", &StereoBank::stereo, "bool[nchan]: pilot_level > threshold")
+        .def("__call__", &StereoBank::call, "float32[nchan, K] -> float32[nchan, 2, ncols] (left, right)");
 
     // ---- AudioBank (beyond the reference: de-emphasis and resampler over bank rows)
     py::class_<AudioBank>(m, "AudioBank")
