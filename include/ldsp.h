@@ -942,6 +942,89 @@ int ldsp_stbank_get_pilot_level(ldsp_stbank_t q, float *level);  /* C floats */
 int ldsp_debug_stbank_tile(unsigned int D, unsigned int L, size_t *frames);
 
 /* ------------------------------------------------------------------------
+ * AMBank: a feed-forward coherent AM demodulator over the rows of a bank.  Every
+ * row of a complex64 [C][K] block (a Channelizer, Downconverter or SquelchBank
+ * output) goes to one row of float32 audio, in one launch for all rows.  No
+ * reference counterpart: liquid's ampmodem (AmpModem, BroadcastAM) tracks the
+ * carrier with a per-sample PLL behind an AGC, one stream per object; this
+ * decoder has no loop to lock, and the definition is this library's own.  With
+ * a decimation D, an audio prototype h, a carrier prototype g of the same
+ * length L (real, float32) and a threshold thr, for every row c, with zeros
+ * before the stream's start:
+ *   d[j]     = (float)((double)h[j] - (double)g[j])                (rounded once)
+ *   B[c][n]  = sum_{j<L} d[j] x[c][nD-j]      (complex: the audio band, the carrier taken out)
+ *   Cr[c][n] = sum_{j<L} g[j] x[c][nD-j]      (complex: the carrier)
+ *   m        = |Cr|^2                         (float32, on the value the kernel holds)
+ *   y[c][n]  = m > thr^2 ? Re(B conj(Cr)) / m : 0                  (thr^2 = thr * thr in float32)
+ * For x = A (1 + a(t)) exp(i (2 pi f0 t + phi)) with f0 inside g's pass band, Cr
+ * is the carrier and B is A a(t) exp(i theta), so y = a(t) delayed by
+ * (L - 1) / 2 input samples: full scale +-1 is 100 % modulation whatever A, phi
+ * and f0 are, nothing is tracked from column to column, there is no AGC, and a
+ * row has no serial state but its last L - 1 raw samples.  B is formed with d
+ * and not as (h * x) - Cr, so the carrier never has to cancel in float32.  A row
+ * of zeros (a block a SquelchBank closed) gives m = 0 and y = +0, never 0 / 0,
+ * at any threshold.  m, the product and the division are single float32
+ * operations (the two sums of two products each one fused multiply-add).
+ * Every row of y is within 1e-6 of the float64 evaluation of the definition
+ * (max-norm, absolute: against the scale of the carrier, y = 1 being 100 %)
+ * wherever |B| <= |Cr|, which is every column of a row with a carrier once its
+ * window lies inside the stream.  Where |B| > |Cr| (the first columns of a
+ * stream, whose carrier estimate is a few edge taps, and rows without a carrier
+ * at a low threshold) y is unbounded and the error is within 1e-6 of
+ * SB / |Cr| + |B| SC / |Cr|^2, SB = sum |d[j] x|, SC = sum |g[j] x|.
+ * The column schedule is the Channelizer's and the FMBank's: output n is
+ * emitted by the call that delivers sample nD of every row; with T samples per
+ * row seen before a call and skip = (-T) mod D, a call of K samples per row
+ * returns K > skip ? ceil((K - skip) / D) : 0 columns; calls of any K, 0
+ * included, are allowed.  A row's bits depend neither on how the stream is cut
+ * into calls, nor on the other rows, their number or order, nor on the row
+ * strides.
+ *   1 <= C <= 256, fixed at creation;  1 <= D <= 32;  1 <= L <= 1025;
+ *   0 < carrier < audio <= 0.5 (cycles per row sample);  thr >= 0;  as > 0.
+ * ldsp_ambank_create designs, with audio = 0 standing for 0.5 / D (0.45 when
+ * D = 1) and L = 0 for 2 ceil(2 / carrier) + 1 (1001 at carrier = 0.004; a 60 dB
+ * Kaiser's transition is then about 0.9 carrier and g stops from about
+ * 1.45 carrier),
+ *   h = firdes_kaiser(L, (float)audio, as, 0),
+ *   g = firdes_kaiser(L, (float)carrier, as, 0),
+ * each tap then divided in double by the double sum of the float32 design and
+ * rounded once (unit DC gain).  ldsp_ambank_create_taps takes h and g as given;
+ * they must have the same length.  A value out of range (a NaN among them), a
+ * NULL pointer and prototypes of unequal length are LDSP_EINVAL; a default L
+ * above 1025 (carrier below 2 / 512) is LDSP_EUNSUP.
+ * ldsp_ambank_set_threshold takes effect at the next call and touches no state.
+ * ldsp_ambank_execute reads row c at x + c * ldx and writes row c at
+ * y + c * ldy (all in samples, ldx >= K): the output is a [C][ncols] image an
+ * AudioBank(C, ...) reads in place.  It sets *ncols and, when ldy < *ncols,
+ * returns LDSP_ERANGE without consuming the input.  Argument errors are decided
+ * on the host before any device work.
+ * ldsp_ambank_get_carrier_level copies out, per row, sqrtf(m) of the last
+ * column emitted (0 before any); it waits for the last call.
+ * Not built: a per-row carrier offset or search, suppressed-carrier and SSB
+ * rows, a two-stage (decimate first) carrier estimate, envelope output,
+ * skipping closed rows, any change of AmpModem / BroadcastAM / execute_many.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_ambank_s *ldsp_ambank_t;
+/* audio = 0: the default cut-off;  L = 0: the default length. */
+int ldsp_ambank_create(unsigned int C, unsigned int D, double audio, double carrier, unsigned int L, float as,
+                       float threshold, ldsp_ambank_t *q);
+int ldsp_ambank_create_taps(unsigned int C, unsigned int D, const float *h, unsigned int L, const float *g,
+                            unsigned int Lg, float threshold, ldsp_ambank_t *q);
+int ldsp_ambank_destroy(ldsp_ambank_t q);
+int ldsp_ambank_reset(ldsp_ambank_t q);
+/* Any pointer may be NULL.  skip: input samples per row before the next call's first output. */
+int ldsp_ambank_get_info(ldsp_ambank_t q, unsigned int *C, unsigned int *D, unsigned int *L, unsigned int *skip);
+int ldsp_ambank_get_taps(ldsp_ambank_t q, float *h, float *g, float *d);   /* L floats each; any may be NULL */
+int ldsp_ambank_get_threshold(ldsp_ambank_t q, float *thr);
+int ldsp_ambank_set_threshold(ldsp_ambank_t q, float thr);
+int ldsp_ambank_num_outputs(ldsp_ambank_t q, size_t K, size_t *ncols);
+int ldsp_ambank_execute(ldsp_ambank_t q, const void *x, size_t ldx, size_t K, void *y, size_t ldy, size_t *ncols,
+                        int mem, void *stream);
+int ldsp_ambank_get_carrier_level(ldsp_ambank_t q, float *level);  /* C floats */
+/* Test hook: output columns per workgroup of the (D, L) kernel. */
+int ldsp_debug_ambank_tile(unsigned int D, unsigned int L, size_t *frames);
+
+/* ------------------------------------------------------------------------
  * Spectrogram: a streaming Welch periodogram, one complex64 stream to rows of
  * power per bin and a running mean of them.  No reference counterpart
  * (liquid's spgramcf / spwaterfallcf are the same block: a zeroed window

@@ -1483,6 +1483,41 @@ struct ldsp_stbank_s : ldsp::DevObj, Decimating<ldsp_stbank_s> {
     }
 };
 
+// AMBank (coherent AM demodulator over bank rows): the audio and the carrier
+// prototype and their difference d, the threshold, the host-side stream position
+// (skip follows from it), and on the device the tap table in the kernel's layout
+// (kernels.hpp), per row the last L - 1 raw complex samples, ping-ponged, and
+// per row the carrier level of the last column emitted.  The history is raw
+// input, so a new threshold touches no state.
+struct ldsp_ambank_s : ldsp::DevObj, Decimating<ldsp_ambank_s> {
+    unsigned int C = 0, D = 1;
+    float thr = 0.0f;
+    std::vector<float> h, g, d;            // audio and carrier prototypes, the same length; d = h - g, rounded once
+    uint64_t seen = 0;                     // input samples per row since create / reset
+    ldsp::DevBuf dtaps, dlevel;
+    ldsp::PingPong hist;
+    size_t hist_bytes() const { return std::max<size_t>((size_t)C * (h.size() - 1), 1) * 8; }
+    void zero_state(int dev)
+    {
+        hist.zero(hist_bytes(), dev);
+        ldsp::zero_now(dlevel.ensure((size_t)C * 4, dev), 0, (size_t)C * 4);
+    }
+    void bind(int dev)
+    {
+        const size_t L = h.size();
+        std::vector<float> t(4 * L, 0.0f);
+        for (size_t j = 0; j < L; j++) {
+            float* e = &t[4 * (L - 1 - j)];
+            e[0] = d[j];
+            e[1] = g[j];
+            const int slot = ldsp::k::ambank_slot((int)D, (int)L, (int)(L - 1 - j));
+            std::memcpy(&e[2], &slot, 4);
+        }
+        ldsp::upload(dtaps, t, dev);
+        zero_state(dev);
+    }
+};
+
 // Spectrogram (streaming Welch periodogram): the window, the host-side counts
 // (samples since reset, transforms since clear; the schedule follows from
 // them), and on the device the padded window, the twiddle table, the last
@@ -4556,6 +4591,176 @@ int ldsp_debug_stbank_tile(unsigned int D, unsigned int L, size_t* frames)
                      "stbank: the decimation must lie in 1 .. " + std::to_string(k::kStbankMaxD));
         stbank_check_length(L);
         *frames = (size_t)k::stbank_frames((int)D, (int)L);
+    });
+}
+
+// ---------------------------------------------------------------- AMBank
+static void ambank_check_shape(unsigned int C, unsigned int D, float thr)
+{
+    LDSP_REQUIRE(C >= 1 && C <= (unsigned)k::kAmbankMaxC,
+                 "ambank: the row count must lie in 1 .. " + std::to_string(k::kAmbankMaxC));
+    LDSP_REQUIRE(D >= 1 && D <= (unsigned)k::kAmbankMaxD,
+                 "ambank: the decimation must lie in 1 .. " + std::to_string(k::kAmbankMaxD));
+    LDSP_REQUIRE(thr >= 0.0f, "ambank: the carrier threshold must be >= 0");
+}
+static void ambank_check_length(unsigned int L)
+{
+    LDSP_REQUIRE(L >= 1 && L <= (unsigned)k::kAmbankMaxL,
+                 "ambank: the prototype length must lie in 1 .. " + std::to_string(k::kAmbankMaxL));
+}
+// d[j] = (float)((double)h[j] - (double)g[j]): the audio band with the carrier taken out, rounded once
+static ldsp_ambank_s* ambank_make(unsigned int C, unsigned int D, float thr, std::vector<float> h, std::vector<float> g)
+{
+    std::unique_ptr<ldsp_ambank_s> o(new ldsp_ambank_s());
+    o->C = C;
+    o->D = D;
+    o->thr = thr;
+    o->d.resize(h.size());
+    for (size_t j = 0; j < h.size(); j++) o->d[j] = (float)((double)h[j] - (double)g[j]);
+    o->h = std::move(h);
+    o->g = std::move(g);
+    return o.release();
+}
+int ldsp_ambank_create(unsigned int C, unsigned int D, double audio, double carrier, unsigned int L, float as,
+                       float threshold, ldsp_ambank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        ambank_check_shape(C, D, threshold);
+        if (audio == 0.0) audio = D == 1 ? 0.45 : 0.5 / (double)D;   // the default audio cut-off
+        LDSP_REQUIRE(carrier > 0.0 && carrier < audio && audio <= 0.5,
+                     "ambank: the cut-offs must satisfy 0 < carrier < audio <= 0.5 cycles per sample");
+        LDSP_REQUIRE(as > 0.0f, "ambank: stop-band attenuation must be > 0");
+        if (L == 0) {                                 // the default length
+            const double half = std::ceil(2.0 / carrier);
+            if (2.0 * half + 1.0 > (double)k::kAmbankMaxL)
+                throw Error(LDSP_EUNSUP, "ambank: a default prototype above " + std::to_string(k::kAmbankMaxL) +
+                                             " taps is not implemented (carrier cut-off too low)");
+            L = 2 * (unsigned)half + 1;
+        }
+        ambank_check_length(L);
+        *q = ambank_make(C, D, threshold, stbank_design(L, audio, as), stbank_design(L, carrier, as));
+    });
+}
+int ldsp_ambank_create_taps(unsigned int C, unsigned int D, const float* h, unsigned int L, const float* g, unsigned int Lg,
+                            float threshold, ldsp_ambank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        ambank_check_shape(C, D, threshold);
+        ambank_check_length(L);
+        LDSP_REQUIRE(Lg == L, "ambank: the audio and the carrier prototype must have the same length");
+        NONNULL(h);
+        NONNULL(g);
+        *q = ambank_make(C, D, threshold, std::vector<float>(h, h + L), std::vector<float>(g, g + L));
+    });
+}
+int ldsp_ambank_destroy(ldsp_ambank_t q) { return guard([&] { destroy(q); }); }
+int ldsp_ambank_reset(ldsp_ambank_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        q->seen = 0;
+        q->at_rest([&] { q->zero_state(q->device); });
+    });
+}
+int ldsp_ambank_get_info(ldsp_ambank_t q, unsigned int* C, unsigned int* D, unsigned int* L, unsigned int* skip)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (C) *C = q->C;
+        if (D) *D = q->D;
+        if (L) *L = (unsigned)q->h.size();
+        if (skip) *skip = (unsigned)q->skip();
+    });
+}
+int ldsp_ambank_get_taps(ldsp_ambank_t q, float* h, float* g, float* d)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (h) std::copy(q->h.begin(), q->h.end(), h);
+        if (g) std::copy(q->g.begin(), q->g.end(), g);
+        if (d) std::copy(q->d.begin(), q->d.end(), d);
+    });
+}
+int ldsp_ambank_get_threshold(ldsp_ambank_t q, float* t) { return guard([&] { NONNULL(q); NONNULL(t); *t = q->thr; }); }
+int ldsp_ambank_set_threshold(ldsp_ambank_t q, float t)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(t >= 0.0f, "ambank: the carrier threshold must be >= 0");
+        q->thr = t;                                   // a kernel argument of the next call
+    });
+}
+int ldsp_ambank_num_outputs(ldsp_ambank_t q, size_t K, size_t* ncols)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(ncols);
+        *ncols = q->num_outputs(K);
+    });
+}
+int ldsp_ambank_execute(ldsp_ambank_t q, const void* x, size_t ldx, size_t K, void* y, size_t ldy, size_t* ncols, int mem,
+                        void* stream)
+{
+    LDSP_RANGE("ldsp_ambank_execute");
+    return guard([&] {
+        NONNULL(q);
+        const size_t N = q->num_outputs(K);
+        if (ncols) *ncols = N;
+        LDSP_REQUIRE(ldx >= K, "ambank_execute: input row stride below the number of samples");
+        if (N > ldy) throw Error(LDSP_ERANGE, "ambank_execute: output row stride below the number of output columns");
+        LDSP_REQUIRE(K == 0 || x, "ambank_execute: NULL input");
+        LDSP_REQUIRE(N == 0 || y, "ambank_execute: NULL output");
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
+        const size_t C = q->C;
+        // a host-memory call reads and writes dense [C][K] and [C][N] device images
+        // (rows of the caller's images are ldx and ldy samples apart)
+        const void* dx = q->stg.dev_in(e, x, K * 8, C, ldx * 8);
+        float* dy = (float*)q->stg.dev_out(e, y, C * N * 4);
+        if (K > 0) {
+            k::AmbankCall c;
+            c.x = dx;
+            c.hist = q->hist.in();
+            c.hist_out = q->hist.out();
+            c.n = K;
+            c.ldx = e.host ? K : ldx;
+            c.skip = q->skip();
+            c.ncols = N;
+            c.ldy = e.host ? N : ldy;
+            c.C = (int)C;
+            c.D = (int)q->D;
+            c.L = (int)q->h.size();
+            c.taps = q->dtaps.as<float>();
+            c.thr2 = q->thr * q->thr;
+            c.y = dy;
+            c.level = q->dlevel.as<float>();
+            k::ambank(c, e.stream);
+            q->hist.flip();
+            q->seen += K;
+        }
+        call.end();
+        q->stg.finish(e, y, N * 4, C, ldy * 4);
+    });
+}
+int ldsp_ambank_get_carrier_level(ldsp_ambank_t q, float* level)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(level);
+        std::fill(level, level + q->C, 0.0f);         // before the first call: nothing on the device yet
+        q->at_rest([&] { LDSP_HIP(hipMemcpy(level, q->dlevel.p, (size_t)q->C * 4, hipMemcpyDeviceToHost)); });
+    });
+}
+int ldsp_debug_ambank_tile(unsigned int D, unsigned int L, size_t* frames)
+{
+    return guard([&] {
+        NONNULL(frames);
+        LDSP_REQUIRE(D >= 1 && D <= (unsigned)k::kAmbankMaxD,
+                     "ambank: the decimation must lie in 1 .. " + std::to_string(k::kAmbankMaxD));
+        ambank_check_length(L);
+        *frames = (size_t)k::ambank_frames((int)D, (int)L);
     });
 }
 

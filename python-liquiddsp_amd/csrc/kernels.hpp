@@ -559,6 +559,34 @@ struct StbankCall {
     float* level;
 };
 void stbank(const StbankCall& c, hipStream_t s);
+// k_ambank.hip: coherent AM demodulator over bank rows (AMBank).  C <= kAmbankMaxC
+// rows of complex64, row c's n samples at x + c * ldx (in samples); decimation
+// 1 <= D <= kAmbankMaxD, two real prototypes of L <= kAmbankMaxL taps.  hist /
+// hist_out: per row the L - 1 raw samples before x[c][0] / before the next
+// call's first, [C][L - 1] complex64, distinct buffers (at least one readable
+// sample when L = 1).  The call's columns are at sample skip + m D, m < ncols, as
+// k_chan's.  taps: the host's table [L][4] indexed by k = L - 1 - j: d[j], g[j]
+// (ldsp.h), the bits of ambank_slot(D, L, k) and one word of padding.  thr2: the
+// float32 square of the carrier threshold.  y[c * ldy + m] receives row c's
+// output; level[c] receives sqrtf(|Cr|^2) of the call's last column (untouched
+// by a call without columns).  n = 0 launches nothing.
+constexpr int kAmbankMaxC = 256;
+constexpr int kAmbankMaxD = 32;
+constexpr int kAmbankMaxL = 1025;
+int ambank_frames(int D, int L);                            // output columns per workgroup
+int ambank_slot(int D, int L, int k);                       // where the staged span keeps offset k of column 0, in pairs
+struct AmbankCall {
+    const void* x;
+    const void* hist;
+    void* hist_out;
+    size_t n, ldx, skip, ncols, ldy;
+    int C, D, L;
+    const float* taps;
+    float thr2;
+    float* y;
+    float* level;
+};
+void ambank(const AmbankCall& c, hipStream_t s);
 // k_synth.hip: polyphase synthesis filter bank (Synthesizer), k_chan's
 // counterpart.  M rows (a power of two, 4 .. 256), interpolation D = M or M / 2,
 // Q = ceil(L / D) <= synth_qmax(M, D) taps per output residue.  y: row k at

@@ -1345,6 +1345,93 @@ struct StereoBank {
     }
 };
 
+// ------------------------------------------------------------------ AMBank (no reference counterpart; AmpModem is another demodulator)
+// Feed-forward coherent AM demodulator over bank rows (ldsp.h): complex64[nchan, K]
+// -> float32[nchan, ncols], an AudioBank's input.  Input as the FMBank's: a
+// Channelizer output, a block of rows or a range of columns of one is read in place.
+struct AMBank {
+    Handle<ldsp_ambank_t, ldsp_ambank_destroy> q;
+    unsigned C = 0, D = 0, L = 0;
+    AMBank(int nchan, int decim, const py::object& audio, double carrier, const py::object& ntaps, float as, float thr,
+           const py::object& taps, const py::object& ctaps)
+    {
+        if (nchan < 0) throw py::value_error("AMBank: nchan must lie in 1 .. 256");
+        if (decim < 0) throw py::value_error("AMBank: decim must lie in 1 .. 32");
+        if (taps.is_none() != ctaps.is_none()) throw py::value_error("AMBank: taps and carrier_taps come together");
+        if (!taps.is_none()) {
+            if (!ntaps.is_none()) throw py::value_error("AMBank: ntaps or taps, not both");
+            std::vector<float> h = to_fvec(taps), g = to_fvec(ctaps);
+            check(ldsp_ambank_create_taps((unsigned)nchan, (unsigned)decim, h.data(), (unsigned)h.size(), g.data(),
+                                          (unsigned)g.size(), thr, q.out()));
+        } else {
+            const long n = ntaps.is_none() ? 0 : ntaps.cast<long>();
+            if (!ntaps.is_none() && (n < 1 || n > 1025)) throw py::value_error("AMBank: ntaps must lie in 1 .. 1025");
+            const double fa = audio.is_none() ? 0.0 : audio.cast<double>();
+            if (!audio.is_none() && !(fa > 0.0)) throw py::value_error("AMBank: audio must lie in (carrier, 0.5]");
+            check(ldsp_ambank_create((unsigned)nchan, (unsigned)decim, fa, carrier, (unsigned)n, as, thr, q.out()));
+        }
+        check(ldsp_ambank_get_info(q, &C, &D, &L, nullptr));
+    }
+    void reset() { check(ldsp_ambank_reset(q)); }
+    py::array_t<float> taps()
+    {
+        py::array_t<float> h(L);
+        check(ldsp_ambank_get_taps(q, h.mutable_data(), nullptr, nullptr));
+        return h;
+    }
+    py::array_t<float> carrier_taps()
+    {
+        py::array_t<float> g(L);
+        check(ldsp_ambank_get_taps(q, nullptr, g.mutable_data(), nullptr));
+        return g;
+    }
+    py::array_t<float> band_taps()
+    {
+        py::array_t<float> d(L);
+        check(ldsp_ambank_get_taps(q, nullptr, nullptr, d.mutable_data()));
+        return d;
+    }
+    float get_threshold() { return get_value<float>(ldsp_ambank_get_threshold, q); }
+    void set_threshold(float t) { check(ldsp_ambank_set_threshold(q, t)); }
+    unsigned skip()
+    {
+        unsigned s;
+        check(ldsp_ambank_get_info(q, nullptr, nullptr, nullptr, &s));
+        return s;
+    }
+    size_t tile()
+    {
+        size_t f = 0;
+        check(ldsp_debug_ambank_tile(D, L, &f));
+        return f;
+    }
+    size_t num_outputs(size_t K)
+    {
+        size_t c = 0;
+        check(ldsp_ambank_num_outputs(q, K, &c));
+        return c;
+    }
+    py::array_t<float> carrier_level()
+    {
+        py::array_t<float> v(C);
+        check(ldsp_ambank_get_carrier_level(q, v.mutable_data()));
+        return v;
+    }
+    py::array_t<bool> carrier_present()
+    {
+        const py::array_t<float> v = carrier_level();
+        const float t = get_threshold();
+        py::array_t<bool> s(C);
+        for (unsigned c = 0; c < C; c++) s.mutable_at(c) = v.at(c) > t;
+        return s;
+    }
+    py::object call(const py::handle& x)
+    {
+        return run_from_rows(q.get(), in_rows(x, Kind::c64, C, "AMBank", true, Strided::refuse), Kind::f32, C,
+                             ldsp_ambank_num_outputs, ldsp_ambank_execute);
+    }
+};
+
 // ------------------------------------------------------------------ AudioBank (liquid: iirfilt_rrrf + resamp_rrrf per row)
 // De-emphasis and arbitrary-rate resampler over bank rows (ldsp.h): float32[nchan, K]
 // -> float32[nchan, nout] (int16 with pcm16).  A device tensor whose columns are
@@ -2206,6 +2293,30 @@ PYBIND11_MODULE(_liquiddsp, m)
                                "float32[nchan]: |P| of the last column emitted per row, 0 before any")
         .def_property_readonly("stereo", &StereoBank::stereo, "bool[nchan]: pilot_level > threshold")
         .def("__call__", &StereoBank::call, "float32[nchan, K] -> float32[nchan, 2, ncols] (left, right)");
+
+    // ---- AMBank (beyond the reference: feed-forward coherent AM demodulator over bank rows)
+    py::class_<AMBank>(m, "AMBank")
+        .def(py::init<int, int, py::object, double, py::object, float, float, py::object, py::object>(), py::arg("nchan"),
+             py::arg("decim") = 1, py::arg("audio") = py::none(), py::arg("carrier") = 0.004,
+             py::arg("ntaps") = py::none(), py::arg("As") = 60.0f, py::arg("threshold") = 0.0f,
+             py::arg("taps") = py::none(), py::arg("carrier_taps") = py::none())
+        .def("reset", &AMBank::reset)
+        .def("num_outputs", &AMBank::num_outputs, py::arg("K"),
+             "columns the next call returns for K input samples per row")
+        .def_property_readonly("nchan", [](AMBank& c) { return c.C; })
+        .def_property_readonly("decim", [](AMBank& c) { return c.D; })
+        .def_property_readonly("ntaps", [](AMBank& c) { return c.L; })
+        .def_property_readonly("taps", &AMBank::taps, "the audio prototype h")
+        .def_property_readonly("carrier_taps", &AMBank::carrier_taps, "the carrier prototype g")
+        .def_property_readonly("band_taps", &AMBank::band_taps, "d = h - g as float32, the taps of the audio band")
+        .def_property("threshold", &AMBank::get_threshold, &AMBank::set_threshold,
+                      "carrier amplitude |Cr| above which a column is demodulated; set from the next call on")
+        .def_property_readonly("skip", &AMBank::skip, "input samples per row before the next call's first output")
+        .def_property_readonly("tile", &AMBank::tile, "output columns per workgroup of the kernel")
+        .def_property_readonly("carrier_level", &AMBank::carrier_level,
+                               "float32[nchan]: |Cr| of the last column emitted per row, 0 before any")
+        .def_property_readonly("carrier_present", &AMBank::carrier_present, "bool[nchan]: carrier_level > threshold")
+        .def("__call__", &AMBank::call, "complex64[nchan, K] -> float32[nchan, ncols]");
 
     // ---- AudioBank (beyond the reference: de-emphasis and resampler over bank rows)
     py::class_<AudioBank>(m, "AudioBank")
