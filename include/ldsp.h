@@ -1000,9 +1000,10 @@ int ldsp_debug_stbank_tile(unsigned int D, unsigned int L, size_t *frames);
  * on the host before any device work.
  * ldsp_ambank_get_carrier_level copies out, per row, sqrtf(m) of the last
  * column emitted (0 before any); it waits for the last call.
- * Not built: a per-row carrier offset or search, suppressed-carrier and SSB
- * rows, a two-stage (decimate first) carrier estimate, envelope output,
- * skipping closed rows, any change of AmpModem / BroadcastAM / execute_many.
+ * Not built: a per-row carrier offset or search, suppressed-carrier (DSB-SC)
+ * rows (single-sideband rows are the SSBBank's), a two-stage (decimate first)
+ * carrier estimate, envelope output, skipping closed rows, any change of
+ * AmpModem / BroadcastAM / execute_many.
  * ---------------------------------------------------------------------- */
 typedef struct ldsp_ambank_s *ldsp_ambank_t;
 /* audio = 0: the default cut-off;  L = 0: the default length. */
@@ -1023,6 +1024,100 @@ int ldsp_ambank_execute(ldsp_ambank_t q, const void *x, size_t ldx, size_t K, vo
 int ldsp_ambank_get_carrier_level(ldsp_ambank_t q, float *level);  /* C floats */
 /* Test hook: output columns per workgroup of the (D, L) kernel. */
 int ldsp_debug_ambank_tile(unsigned int D, unsigned int L, size_t *frames);
+
+/* ------------------------------------------------------------------------
+ * SSBBank: a tuned single-sideband demodulator over the rows of a bank.  Every
+ * row of a complex64 [C][K] block (a Channelizer, Downconverter or SquelchBank
+ * output) goes to one row of float32 audio, in one launch for all rows; each
+ * row has its own beat-frequency oscillator (BFO: the position of the
+ * suppressed carrier inside the row) and its own sideband.  The reference's
+ * counterpart (ampmodem's SSB modes, SSBDemod here) is one stream per object
+ * through a Hilbert filter and cannot be tuned; the definition is this
+ * library's own.  With a decimation D, a real low-pass prototype p of L taps, a
+ * band (lo, hi) in cycles per row sample measured from the carrier, and for row
+ * c a BFO bfo_c in [-0.5, 0.5] and a sideband s_c (+1 upper, -1 lower), with
+ * zeros before the stream's start:
+ *   w_c      = rint(bfo_c 2^32) mod 2^32                     32-bit BFO word (0.5 is the word of -0.5)
+ *   wm       = rint(((lo + hi) / 2) 2^32)                    band-centre word
+ *   psi_c[j] = (s_c wm (2j - (L-1)) + 2 j w_c) mod 2^33      integer, counts of 2^-33 turn
+ *   g_c[j]   = p[j] exp(2 pi i psi_c[j] / 2^33)              host, double, rounded once to complex64
+ *   S[c][n]  = sum_{j<L} g_c[j] x[c][nD - j]
+ *   rot_c(n) = exp(-2 pi i ((((nD) mod 2^32) w_c) mod 2^32) / 2^32)   n the absolute 64-bit column index
+ *   y[c][n]  = Re(rot_c(n) S[c][n])
+ * This equals Re(sum_j q_c[j] v[nD - j]) with v[t] = x[t] exp(-2 pi i t w_c / 2^32)
+ * (the carrier moved to DC) and q_c[j] = p[j] exp(2 pi i s_c fm (j - (L-1)/2)),
+ * fm = wm / 2^32 (the complex band-pass over the chosen sideband); the split is
+ * exact because the phase is additive modulo 2^32, as in the Downconverter.
+ * For x = (m(t) + i s m^(t)) exp(2 pi i bfo t), m^ the Hilbert transform of m
+ * (liquid's ampmodem SSB convention, gain 1), y is m delayed by (L - 1) / 2
+ * input samples.  Nothing is tracked from column to column, there is no AGC,
+ * and a row has no serial state but its last L - 1 raw samples.  The rotation
+ * is the double sincospi of the exact phase rounded once; S_re = P.x - Q.y and
+ * S_im = P.y + Q.x from the four real sums P = sum Re g (x_re, x_im),
+ * Q = sum Im g (x_re, x_im), and y = fma(cos, S_re, sin * S_im) + 0 are single
+ * float32 operations.  A row of zeros (a block a SquelchBank closed) gives +0.
+ * Every row of y is within 1e-6 of the float64 evaluation of the definition
+ * from the float32 taps g (max-norm, relative to the row's largest output; for
+ * a row whose output is the residue of rejected content, relative to
+ * max_n sum_j |g_c[j]| |x[nD - j]|).
+ * The column schedule is the Channelizer's and the AMBank's: output n is
+ * emitted by the call that delivers sample nD of every row; with T samples per
+ * row seen before a call and skip = (-T) mod D, a call of K samples per row
+ * returns K > skip ? ceil((K - skip) / D) : 0 columns; calls of any K, 0
+ * included, are allowed.  A row's bits depend neither on how the stream is cut
+ * into calls, nor on the other rows, their number or order, nor on the row
+ * strides.
+ *   1 <= C <= 256, fixed at creation;  1 <= D <= 32;  1 <= L <= 1025;
+ *   0 < lo < hi <= 0.5 / D;  |bfo_c| <= 0.5;  s_c = +1 or -1;  as > 0.
+ * hi = 0 stands for 0.5 / D - lo (LDSP_EINVAL if that leaves hi <= lo).
+ * ldsp_ssbbank_create designs, with L = 0 for 2 ceil(1 / lo) + 1 (81 at
+ * lo = 0.025: a 60 dB Kaiser's transition is then about 1.8 lo, the band is
+ * -6 dB at lo and hi and the stop band begins about 0.1 lo above the carrier,
+ * so the carrier and the opposite sideband are both rejected),
+ *   p = firdes_kaiser(L, (float)((hi - lo) / 2), as, 0),
+ * each tap then divided in double by the double sum of the float32 design and
+ * rounded once (unit DC gain).  ldsp_ssbbank_create_taps takes p as given.
+ * bfo and sideband have C entries each.  A value out of range (a NaN among
+ * them) and a NULL pointer are LDSP_EINVAL; a default L above 1025 (lo below
+ * 1 / 512) is LDSP_EUNSUP.
+ * ldsp_ssbbank_set_bfo and ldsp_ssbbank_set_sideband take the whole list of C
+ * entries and take effect at the next call; the history is raw input and is
+ * not touched, and the device tables are replaced once the object's earlier
+ * calls have finished.
+ * ldsp_ssbbank_execute reads row c at x + c * ldx and writes row c at
+ * y + c * ldy (all in samples, ldx >= K): the output is a [C][ncols] image an
+ * AudioBank(C, ...) reads in place.  It sets *ncols and, when ldy < *ncols,
+ * returns LDSP_ERANGE without consuming the input.  Argument errors are decided
+ * on the host before any device work.
+ * Not built: independent-sideband output (both sidebands of a row at once),
+ * DSB-SC with carrier recovery, a per-row band or decimation, an AGC, an
+ * automatic BFO search, skipping closed rows, any change of SSBDemod /
+ * HilbertTransform / AMBank / execute_many.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_ssbbank_s *ldsp_ssbbank_t;
+/* hi = 0: the default upper edge;  L = 0: the default length. */
+int ldsp_ssbbank_create(unsigned int C, unsigned int D, double lo, double hi, unsigned int L, float as,
+                        const double *bfo, const int *sideband, ldsp_ssbbank_t *q);
+int ldsp_ssbbank_create_taps(unsigned int C, unsigned int D, const float *p, unsigned int L, double lo, double hi,
+                             const double *bfo, const int *sideband, ldsp_ssbbank_t *q);
+int ldsp_ssbbank_destroy(ldsp_ssbbank_t q);
+int ldsp_ssbbank_reset(ldsp_ssbbank_t q);
+/* Any pointer may be NULL.  skip: input samples per row before the next call's first output. */
+int ldsp_ssbbank_get_info(ldsp_ssbbank_t q, unsigned int *C, unsigned int *D, unsigned int *L, unsigned int *skip);
+int ldsp_ssbbank_get_band(ldsp_ssbbank_t q, double *lo, double *hi);       /* either may be NULL */
+/* p: L floats;  g: C * L complex64 (re, im), row c's g_c[j] at g[2 (c L + j)];  either may be NULL */
+int ldsp_ssbbank_get_taps(ldsp_ssbbank_t q, float *p, float *g);
+int ldsp_ssbbank_get_words(ldsp_ssbbank_t q, uint32_t *w);                 /* C words */
+int ldsp_ssbbank_get_bfo(ldsp_ssbbank_t q, double *bfo);                   /* C doubles, as given */
+int ldsp_ssbbank_set_bfo(ldsp_ssbbank_t q, const double *bfo);             /* C doubles */
+int ldsp_ssbbank_get_sideband(ldsp_ssbbank_t q, int *sideband);            /* C ints, +1 or -1 */
+int ldsp_ssbbank_set_sideband(ldsp_ssbbank_t q, const int *sideband);      /* C ints, +1 or -1 */
+int ldsp_ssbbank_num_outputs(ldsp_ssbbank_t q, size_t K, size_t *ncols);
+int ldsp_ssbbank_execute(ldsp_ssbbank_t q, const void *x, size_t ldx, size_t K, void *y, size_t ldy, size_t *ncols,
+                         int mem, void *stream);
+/* Test hooks: output columns per workgroup of the (D, L) kernel; reset, then stream position T (zero history). */
+int ldsp_debug_ssbbank_tile(unsigned int D, unsigned int L, size_t *frames);
+int ldsp_debug_ssbbank_seek(ldsp_ssbbank_t q, uint64_t T);
 
 /* ------------------------------------------------------------------------
  * Spectrogram: a streaming Welch periodogram, one complex64 stream to rows of

@@ -14,6 +14,7 @@
 #include <iterator>
 #include <map>
 #include <set>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -1515,6 +1516,66 @@ struct ldsp_ambank_s : ldsp::DevObj, Decimating<ldsp_ambank_s> {
         }
         ldsp::upload(dtaps, t, dev);
         zero_state(dev);
+    }
+};
+
+// SSBBank (tuned single-sideband demodulator over bank rows): the prototype, the
+// band, per row the BFO, its word and the sideband, the complex taps g that
+// follow from them (ldsp.h), the host-side stream position (skip and the first
+// column's absolute index follow from it), and on the device the tap table in
+// the kernel's layout (kernels.hpp), the words and per row the last L - 1 raw
+// complex samples, ping-ponged.  The history is raw input, so a retune touches
+// the tables alone.
+struct ldsp_ssbbank_s : ldsp::DevObj, Decimating<ldsp_ssbbank_s> {
+    unsigned int C = 0, D = 1;
+    double lo = 0.0, hi = 0.0;
+    std::vector<float> p;                  // the real low-pass prototype
+    std::vector<double> bfo;               // as given, C entries
+    std::vector<uint32_t> w;               // rint(bfo 2^32) mod 2^32
+    std::vector<int> side;                 // +1 usb, -1 lsb
+    std::vector<float> g;                  // [C][L] (re, im), index j
+    uint64_t seen = 0;                     // input samples per row since create / reset (or the seek hook's T)
+    ldsp::DevBuf dtaps, dwords;
+    ldsp::PingPong hist;
+    size_t hist_bytes() const { return std::max<size_t>((size_t)C * (p.size() - 1), 1) * 8; }
+    uint64_t next_column() const { return seen / D + (seen % D != 0); }
+    // psi_c[j] = (s_c wm (2j - (L - 1)) + 2 j w_c) mod 2^33 in integers, counts of 2^-33 turn;
+    // g_c[j] = p[j] exp(2 pi i psi / 2^33) in double, the phase as a signed count, rounded once
+    void make_taps()
+    {
+        const size_t L = p.size();
+        const int64_t wm = (int64_t)std::nearbyint((lo + hi) * 0.5 * 4294967296.0);
+        const int64_t M = (int64_t)1 << 33;
+        g.assign(2 * (size_t)C * L, 0.0f);
+        for (size_t c = 0; c < C; c++)
+            for (size_t j = 0; j < L; j++) {
+                int64_t psi = ((int64_t)side[c] * wm * (2 * (int64_t)j - (int64_t)(L - 1)) + 2 * (int64_t)j * (int64_t)w[c]) % M;
+                if (psi < 0) psi += M;
+                if (psi >= M / 2) psi -= M;           // [-2^32, 2^32): exact in double
+                const double a = M_PI * ((double)psi / 4294967296.0);
+                g[2 * (c * L + j)] = (float)((double)p[j] * cos(a));
+                g[2 * (c * L + j) + 1] = (float)((double)p[j] * sin(a));
+            }
+    }
+    void upload_tables(int dev)
+    {
+        const size_t L = p.size();
+        std::vector<float> t(4 * (size_t)C * L, 0.0f);
+        for (size_t c = 0; c < C; c++)
+            for (size_t j = 0; j < L; j++) {
+                float* e = &t[4 * (c * L + (L - 1 - j))];
+                e[0] = g[2 * (c * L + j)];
+                e[1] = g[2 * (c * L + j) + 1];
+                const int slot = ldsp::k::ssbbank_slot((int)D, (int)L, (int)(L - 1 - j));
+                std::memcpy(&e[2], &slot, 4);
+            }
+        ldsp::upload(dtaps, t, dev);
+        ldsp::upload(dwords, w, dev);
+    }
+    void bind(int dev)
+    {
+        upload_tables(dev);
+        hist.zero(hist_bytes(), dev);
     }
 };
 
@@ -4761,6 +4822,248 @@ int ldsp_debug_ambank_tile(unsigned int D, unsigned int L, size_t* frames)
                      "ambank: the decimation must lie in 1 .. " + std::to_string(k::kAmbankMaxD));
         ambank_check_length(L);
         *frames = (size_t)k::ambank_frames((int)D, (int)L);
+    });
+}
+
+// ---------------------------------------------------------------- SSBBank
+static void ssbbank_check_length(unsigned int L)
+{
+    LDSP_REQUIRE(L >= 1 && L <= (unsigned)k::kSsbbankMaxL,
+                 "ssbbank: the prototype length must lie in 1 .. " + std::to_string(k::kSsbbankMaxL));
+}
+// The shape and the band: hi = 0 stands for 0.5 / D - lo.  Returns hi.
+static double ssbbank_check_shape(unsigned int C, unsigned int D, double lo, double hi)
+{
+    LDSP_REQUIRE(C >= 1 && C <= (unsigned)k::kSsbbankMaxC,
+                 "ssbbank: the row count must lie in 1 .. " + std::to_string(k::kSsbbankMaxC));
+    LDSP_REQUIRE(D >= 1 && D <= (unsigned)k::kSsbbankMaxD,
+                 "ssbbank: the decimation must lie in 1 .. " + std::to_string(k::kSsbbankMaxD));
+    if (hi == 0.0) hi = 0.5 / (double)D - lo;         // the default upper edge
+    LDSP_REQUIRE(lo > 0.0 && lo < hi && hi <= 0.5 / (double)D,
+                 "ssbbank: the band must satisfy 0 < lo < hi <= 0.5 / D cycles per sample");
+    return hi;
+}
+// w = rint(bfo 2^32) mod 2^32 (the product is exact, rint rounds ties to even); 0.5 is the word of -0.5
+static std::vector<uint32_t> ssbbank_words(const double* bfo, unsigned int C)
+{
+    LDSP_REQUIRE(bfo != nullptr, "bfo must not be NULL");
+    std::vector<uint32_t> w(C);
+    for (unsigned c = 0; c < C; c++) {
+        LDSP_REQUIRE(std::isfinite(bfo[c]) && std::fabs(bfo[c]) <= 0.5,
+                     "ssbbank: a BFO must lie in -0.5 .. 0.5 cycles per row sample");
+        w[c] = (uint32_t)(uint64_t)(int64_t)std::nearbyint(bfo[c] * 4294967296.0);
+    }
+    return w;
+}
+static std::vector<int> ssbbank_sides(const int* s, unsigned int C)
+{
+    LDSP_REQUIRE(s != nullptr, "sideband must not be NULL");
+    for (unsigned c = 0; c < C; c++) LDSP_REQUIRE(s[c] == 1 || s[c] == -1, "ssbbank: a sideband is +1 (usb) or -1 (lsb)");
+    return std::vector<int>(s, s + C);
+}
+static ldsp_ssbbank_s* ssbbank_make(unsigned int C, unsigned int D, double lo, double hi, std::vector<float> p,
+                                    const double* bfo, const int* sideband)
+{
+    std::unique_ptr<ldsp_ssbbank_s> o(new ldsp_ssbbank_s());
+    o->C = C;
+    o->D = D;
+    o->lo = lo;
+    o->hi = hi;
+    o->w = ssbbank_words(bfo, C);
+    o->side = ssbbank_sides(sideband, C);
+    o->bfo.assign(bfo, bfo + C);
+    o->p = std::move(p);
+    o->make_taps();
+    return o.release();
+}
+int ldsp_ssbbank_create(unsigned int C, unsigned int D, double lo, double hi, unsigned int L, float as, const double* bfo,
+                        const int* sideband, ldsp_ssbbank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        hi = ssbbank_check_shape(C, D, lo, hi);
+        LDSP_REQUIRE(as > 0.0f, "ssbbank: stop-band attenuation must be > 0");
+        if (L != 0) ssbbank_check_length(L);
+        (void)ssbbank_words(bfo, C);                  // a value out of range comes before a length not implemented
+        (void)ssbbank_sides(sideband, C);
+        if (L == 0) {                                 // the default length
+            const double half = std::ceil(1.0 / lo);
+            if (2.0 * half + 1.0 > (double)k::kSsbbankMaxL)
+                throw Error(LDSP_EUNSUP, "ssbbank: a default prototype above " + std::to_string(k::kSsbbankMaxL) +
+                                             " taps is not implemented (lo too low)");
+            L = 2 * (unsigned)half + 1;
+        }
+        *q = ssbbank_make(C, D, lo, hi, stbank_design(L, (hi - lo) * 0.5, as), bfo, sideband);
+    });
+}
+int ldsp_ssbbank_create_taps(unsigned int C, unsigned int D, const float* p, unsigned int L, double lo, double hi,
+                             const double* bfo, const int* sideband, ldsp_ssbbank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        hi = ssbbank_check_shape(C, D, lo, hi);
+        ssbbank_check_length(L);
+        NONNULL(p);
+        *q = ssbbank_make(C, D, lo, hi, std::vector<float>(p, p + L), bfo, sideband);
+    });
+}
+int ldsp_ssbbank_destroy(ldsp_ssbbank_t q) { return guard([&] { destroy(q); }); }
+static void ssbbank_restart(ldsp_ssbbank_t q, uint64_t T)
+{
+    q->seen = T;
+    q->at_rest([&] { q->hist.zero(q->hist_bytes(), q->device); });
+}
+int ldsp_ssbbank_reset(ldsp_ssbbank_t q) { return guard([&] { NONNULL(q); ssbbank_restart(q, 0); }); }
+int ldsp_debug_ssbbank_seek(ldsp_ssbbank_t q, uint64_t T) { return guard([&] { NONNULL(q); ssbbank_restart(q, T); }); }
+int ldsp_ssbbank_get_info(ldsp_ssbbank_t q, unsigned int* C, unsigned int* D, unsigned int* L, unsigned int* skip)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (C) *C = q->C;
+        if (D) *D = q->D;
+        if (L) *L = (unsigned)q->p.size();
+        if (skip) *skip = (unsigned)q->skip();
+    });
+}
+int ldsp_ssbbank_get_band(ldsp_ssbbank_t q, double* lo, double* hi)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (lo) *lo = q->lo;
+        if (hi) *hi = q->hi;
+    });
+}
+int ldsp_ssbbank_get_taps(ldsp_ssbbank_t q, float* p, float* g)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (p) std::copy(q->p.begin(), q->p.end(), p);
+        if (g) std::copy(q->g.begin(), q->g.end(), g);
+    });
+}
+int ldsp_ssbbank_get_words(ldsp_ssbbank_t q, uint32_t* w)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(w);
+        std::copy(q->w.begin(), q->w.end(), w);
+    });
+}
+int ldsp_ssbbank_get_bfo(ldsp_ssbbank_t q, double* bfo)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(bfo);
+        std::copy(q->bfo.begin(), q->bfo.end(), bfo);
+    });
+}
+int ldsp_ssbbank_get_sideband(ldsp_ssbbank_t q, int* sideband)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(sideband);
+        std::copy(q->side.begin(), q->side.end(), sideband);
+    });
+}
+// A retune: new taps on the host, and the device tables change only once the
+// object's earlier calls have finished with them; on a failure the old lists stay
+static void ssbbank_retune(ldsp_ssbbank_t q, const std::function<void()>& change)
+{
+    std::vector<double> bfo = q->bfo;
+    std::vector<uint32_t> w = q->w;
+    std::vector<int> side = q->side;
+    std::vector<float> g = q->g;
+    change();
+    try {
+        q->make_taps();
+        q->at_rest([&] { q->upload_tables(q->device); });
+    } catch (...) {
+        q->bfo.swap(bfo);
+        q->w.swap(w);
+        q->side.swap(side);
+        q->g.swap(g);
+        throw;
+    }
+}
+int ldsp_ssbbank_set_bfo(ldsp_ssbbank_t q, const double* bfo)
+{
+    return guard([&] {
+        NONNULL(q);
+        std::vector<uint32_t> w = ssbbank_words(bfo, q->C);
+        ssbbank_retune(q, [&] {
+            q->w = std::move(w);
+            q->bfo.assign(bfo, bfo + q->C);
+        });
+    });
+}
+int ldsp_ssbbank_set_sideband(ldsp_ssbbank_t q, const int* sideband)
+{
+    return guard([&] {
+        NONNULL(q);
+        std::vector<int> s = ssbbank_sides(sideband, q->C);
+        ssbbank_retune(q, [&] { q->side = std::move(s); });
+    });
+}
+int ldsp_ssbbank_num_outputs(ldsp_ssbbank_t q, size_t K, size_t* ncols)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(ncols);
+        *ncols = q->num_outputs(K);
+    });
+}
+int ldsp_ssbbank_execute(ldsp_ssbbank_t q, const void* x, size_t ldx, size_t K, void* y, size_t ldy, size_t* ncols, int mem,
+                         void* stream)
+{
+    LDSP_RANGE("ldsp_ssbbank_execute");
+    return guard([&] {
+        NONNULL(q);
+        const size_t N = q->num_outputs(K);
+        if (ncols) *ncols = N;
+        LDSP_REQUIRE(ldx >= K, "ssbbank_execute: input row stride below the number of samples");
+        if (N > ldy) throw Error(LDSP_ERANGE, "ssbbank_execute: output row stride below the number of output columns");
+        LDSP_REQUIRE(K == 0 || x, "ssbbank_execute: NULL input");
+        LDSP_REQUIRE(N == 0 || y, "ssbbank_execute: NULL output");
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
+        const size_t C = q->C;
+        // a host-memory call reads and writes dense [C][K] and [C][N] device images
+        // (rows of the caller's images are ldx and ldy samples apart)
+        const void* dx = q->stg.dev_in(e, x, K * 8, C, ldx * 8);
+        float* dy = (float*)q->stg.dev_out(e, y, C * N * 4);
+        if (K > 0) {
+            k::SsbbankCall c;
+            c.x = dx;
+            c.hist = q->hist.in();
+            c.hist_out = q->hist.out();
+            c.n = K;
+            c.ldx = e.host ? K : ldx;
+            c.skip = q->skip();
+            c.ncols = N;
+            c.ldy = e.host ? N : ldy;
+            c.col0 = q->next_column();
+            c.C = (int)C;
+            c.D = (int)q->D;
+            c.L = (int)q->p.size();
+            c.taps = q->dtaps.as<float>();
+            c.words = q->dwords.as<uint32_t>();
+            c.y = dy;
+            k::ssbbank(c, e.stream);
+            q->hist.flip();
+            q->seen += K;
+        }
+        call.end();
+        q->stg.finish(e, y, N * 4, C, ldy * 4);
+    });
+}
+int ldsp_debug_ssbbank_tile(unsigned int D, unsigned int L, size_t* frames)
+{
+    return guard([&] {
+        NONNULL(frames);
+        LDSP_REQUIRE(D >= 1 && D <= (unsigned)k::kSsbbankMaxD,
+                     "ssbbank: the decimation must lie in 1 .. " + std::to_string(k::kSsbbankMaxD));
+        ssbbank_check_length(L);
+        *frames = (size_t)k::ssbbank_frames((int)D, (int)L);
     });
 }
 

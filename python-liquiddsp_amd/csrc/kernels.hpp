@@ -587,6 +587,34 @@ struct AmbankCall {
     float* level;
 };
 void ambank(const AmbankCall& c, hipStream_t s);
+// k_ssbbank.hip: tuned single-sideband demodulator over bank rows (SSBBank).
+// C <= kSsbbankMaxC rows of complex64, row c's n samples at x + c * ldx (in
+// samples); decimation 1 <= D <= kSsbbankMaxD, per row L <= kSsbbankMaxL complex
+// taps.  hist / hist_out: per row the L - 1 raw samples before x[c][0] / before
+// the next call's first, [C][L - 1] complex64, distinct buffers (at least one
+// readable sample when L = 1).  The call's columns are at sample skip + m D,
+// m < ncols, as k_chan's; col0 is the absolute index of column m = 0 (the
+// rotation's).  taps: the host's table [C][L][4] indexed by k = L - 1 - j:
+// Re g_c[j], Im g_c[j] (ldsp.h), the bits of ssbbank_slot(D, L, k) and one word
+// of padding.  words: the C 32-bit BFO words.  y[c * ldy + m] receives row c's
+// output.  n = 0 launches nothing.
+constexpr int kSsbbankMaxC = 256;
+constexpr int kSsbbankMaxD = 32;
+constexpr int kSsbbankMaxL = 1025;
+int ssbbank_frames(int D, int L);                           // output columns per workgroup
+int ssbbank_slot(int D, int L, int k);                      // where the staged span keeps offset k of column 0, in pairs
+struct SsbbankCall {
+    const void* x;
+    const void* hist;
+    void* hist_out;
+    size_t n, ldx, skip, ncols, ldy;
+    unsigned long long col0;
+    int C, D, L;
+    const float* taps;
+    const uint32_t* words;
+    float* y;
+};
+void ssbbank(const SsbbankCall& c, hipStream_t s);
 // k_synth.hip: polyphase synthesis filter bank (Synthesizer), k_chan's
 // counterpart.  M rows (a power of two, 4 .. 256), interpolation D = M or M / 2,
 // Q = ceil(L / D) <= synth_qmax(M, D) taps per output residue.  y: row k at

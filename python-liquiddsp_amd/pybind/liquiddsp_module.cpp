@@ -1432,6 +1432,141 @@ struct AMBank {
     }
 };
 
+// ------------------------------------------------------------------ SSBBank (liquid: ampmodem's SSB modes, one untuned stream per object)
+// Tuned single-sideband demodulator over bank rows (ldsp.h): complex64[nchan, K]
+// -> float32[nchan, ncols], an AudioBank's input.  Input as the AMBank's: a
+// Channelizer output, a block of rows or a range of columns of one is read in place.
+struct SSBBank {
+    Handle<ldsp_ssbbank_t, ldsp_ssbbank_destroy> q;
+    unsigned C = 0, D = 0, L = 0;
+    // a scalar or a sequence of n entries
+    static std::vector<double> to_bfos(const py::object& o, size_t n)
+    {
+        if (!py::hasattr(o, "__len__")) return std::vector<double>(n, o.cast<double>());
+        std::vector<double> v = o.cast<std::vector<double>>();
+        if (v.size() != n) throw py::value_error("SSBBank: bfo takes a scalar or one entry per row");
+        return v;
+    }
+    static int to_side(const py::handle& h)
+    {
+        if (py::isinstance<py::str>(h)) {
+            const std::string s = h.cast<std::string>();
+            if (s == "usb") return 1;
+            if (s == "lsb") return -1;
+        }
+        throw py::value_error("SSBBank: a sideband is 'usb' or 'lsb'");
+    }
+    static std::vector<int> to_sides(const py::object& o, size_t n)
+    {
+        if (py::isinstance<py::str>(o)) return std::vector<int>(n, to_side(o));
+        if (!py::hasattr(o, "__len__")) throw py::value_error("SSBBank: a sideband is 'usb' or 'lsb'");
+        std::vector<int> v;
+        for (const py::handle& h : o) v.push_back(to_side(h));
+        if (v.size() != n) throw py::value_error("SSBBank: sideband takes one name or one per row");
+        return v;
+    }
+    SSBBank(int nchan, int decim, double lo, const py::object& hi, const py::object& bfo, const py::object& sideband,
+            const py::object& ntaps, float as, const py::object& taps)
+    {
+        if (nchan < 1 || nchan > 256) throw py::value_error("SSBBank: nchan must lie in 1 .. 256");
+        if (decim < 0) throw py::value_error("SSBBank: decim must lie in 1 .. 32");
+        const double fh = hi.is_none() ? 0.0 : hi.cast<double>();
+        if (!hi.is_none() && !(fh > 0.0)) throw py::value_error("SSBBank: hi must lie in (lo, 0.5 / decim]");
+        const std::vector<double> f = to_bfos(bfo, (size_t)nchan);
+        const std::vector<int> sd = to_sides(sideband, (size_t)nchan);
+        if (!taps.is_none()) {
+            if (!ntaps.is_none()) throw py::value_error("SSBBank: ntaps or taps, not both");
+            std::vector<float> p = to_fvec(taps);
+            check(ldsp_ssbbank_create_taps((unsigned)nchan, (unsigned)decim, p.data(), (unsigned)p.size(), lo, fh, f.data(),
+                                           sd.data(), q.out()));
+        } else {
+            const long n = ntaps.is_none() ? 0 : ntaps.cast<long>();
+            if (!ntaps.is_none() && (n < 1 || n > 1025)) throw py::value_error("SSBBank: ntaps must lie in 1 .. 1025");
+            check(ldsp_ssbbank_create((unsigned)nchan, (unsigned)decim, lo, fh, (unsigned)n, as, f.data(), sd.data(), q.out()));
+        }
+        check(ldsp_ssbbank_get_info(q, &C, &D, &L, nullptr));
+    }
+    void reset() { check(ldsp_ssbbank_reset(q)); }
+    double lo()
+    {
+        double v;
+        check(ldsp_ssbbank_get_band(q, &v, nullptr));
+        return v;
+    }
+    double hi()
+    {
+        double v;
+        check(ldsp_ssbbank_get_band(q, nullptr, &v));
+        return v;
+    }
+    py::array_t<float> taps()
+    {
+        py::array_t<float> p(L);
+        check(ldsp_ssbbank_get_taps(q, p.mutable_data(), nullptr));
+        return p;
+    }
+    py::array_t<cf> row_taps()
+    {
+        py::array_t<cf> g({(py::ssize_t)C, (py::ssize_t)L});
+        check(ldsp_ssbbank_get_taps(q, nullptr, reinterpret_cast<float*>(g.mutable_data())));
+        return g;
+    }
+    py::array_t<uint32_t> words()
+    {
+        py::array_t<uint32_t> w(C);
+        check(ldsp_ssbbank_get_words(q, w.mutable_data()));
+        return w;
+    }
+    py::array_t<double> get_bfo()
+    {
+        py::array_t<double> f(C);
+        check(ldsp_ssbbank_get_bfo(q, f.mutable_data()));
+        return f;
+    }
+    void set_bfo(const py::object& o)
+    {
+        const std::vector<double> f = to_bfos(o, C);
+        check(ldsp_ssbbank_set_bfo(q, f.data()));
+    }
+    py::list get_sideband()
+    {
+        std::vector<int> s(C);
+        check(ldsp_ssbbank_get_sideband(q, s.data()));
+        py::list l;
+        for (int v : s) l.append(py::str(v > 0 ? "usb" : "lsb"));
+        return l;
+    }
+    void set_sideband(const py::object& o)
+    {
+        const std::vector<int> s = to_sides(o, C);
+        check(ldsp_ssbbank_set_sideband(q, s.data()));
+    }
+    unsigned skip()
+    {
+        unsigned s;
+        check(ldsp_ssbbank_get_info(q, nullptr, nullptr, nullptr, &s));
+        return s;
+    }
+    size_t tile()
+    {
+        size_t f = 0;
+        check(ldsp_debug_ssbbank_tile(D, L, &f));
+        return f;
+    }
+    size_t num_outputs(size_t K)
+    {
+        size_t c = 0;
+        check(ldsp_ssbbank_num_outputs(q, K, &c));
+        return c;
+    }
+    void seek(uint64_t T) { check(ldsp_debug_ssbbank_seek(q, T)); }
+    py::object call(const py::handle& x)
+    {
+        return run_from_rows(q.get(), in_rows(x, Kind::c64, C, "SSBBank", true, Strided::refuse), Kind::f32, C,
+                             ldsp_ssbbank_num_outputs, ldsp_ssbbank_execute);
+    }
+};
+
 // ------------------------------------------------------------------ AudioBank (liquid: iirfilt_rrrf + resamp_rrrf per row)
 // De-emphasis and arbitrary-rate resampler over bank rows (ldsp.h): float32[nchan, K]
 // -> float32[nchan, nout] (int16 with pcm16).  A device tensor whose columns are
@@ -2317,6 +2452,32 @@ PYBIND11_MODULE(_liquiddsp, m)
                                "float32[nchan]: |Cr| of the last column emitted per row, 0 before any")
         .def_property_readonly("carrier_present", &AMBank::carrier_present, "bool[nchan]: carrier_level > threshold")
         .def("__call__", &AMBank::call, "complex64[nchan, K] -> float32[nchan, ncols]");
+
+    // ---- SSBBank (beyond the reference: tuned single-sideband demodulator over bank rows)
+    py::class_<SSBBank>(m, "SSBBank")
+        .def(py::init<int, int, double, py::object, py::object, py::object, py::object, float, py::object>(),
+             py::arg("nchan"), py::arg("decim") = 1, py::arg("lo") = 0.025, py::arg("hi") = py::none(),
+             py::arg("bfo") = 0.0, py::arg("sideband") = "usb", py::arg("ntaps") = py::none(), py::arg("As") = 60.0f,
+             py::arg("taps") = py::none())
+        .def("reset", &SSBBank::reset)
+        .def("num_outputs", &SSBBank::num_outputs, py::arg("K"),
+             "columns the next call returns for K input samples per row")
+        .def("_seek", &SSBBank::seek, py::arg("T"), "test hook: reset, then stream position T (zero history)")
+        .def_property_readonly("nchan", [](SSBBank& c) { return c.C; })
+        .def_property_readonly("decim", [](SSBBank& c) { return c.D; })
+        .def_property_readonly("ntaps", [](SSBBank& c) { return c.L; })
+        .def_property_readonly("lo", &SSBBank::lo, "lower band edge, cycles per row sample from the carrier")
+        .def_property_readonly("hi", &SSBBank::hi, "upper band edge, cycles per row sample from the carrier")
+        .def_property_readonly("taps", &SSBBank::taps, "the real low-pass prototype p")
+        .def_property_readonly("row_taps", &SSBBank::row_taps, "complex64[nchan, ntaps]: the rows' band-pass taps g")
+        .def_property("bfo", &SSBBank::get_bfo, &SSBBank::set_bfo,
+                      "float64[nchan]: the carriers' positions in the rows; set (a scalar or one per row) from the next call on")
+        .def_property_readonly("words", &SSBBank::words, "uint32[nchan]: the 32-bit BFO words")
+        .def_property("sideband", &SSBBank::get_sideband, &SSBBank::set_sideband,
+                      "list of 'usb' / 'lsb' per row; set (one name or one per row) from the next call on")
+        .def_property_readonly("skip", &SSBBank::skip, "input samples per row before the next call's first output")
+        .def_property_readonly("tile", &SSBBank::tile, "output columns per workgroup of the kernel")
+        .def("__call__", &SSBBank::call, "complex64[nchan, K] -> float32[nchan, ncols]");
 
     // ---- AudioBank (beyond the reference: de-emphasis and resampler over bank rows)
     py::class_<AudioBank>(m, "AudioBank")
