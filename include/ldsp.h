@@ -1120,6 +1120,88 @@ int ldsp_debug_ssbbank_tile(unsigned int D, unsigned int L, size_t *frames);
 int ldsp_debug_ssbbank_seek(ldsp_ssbbank_t q, uint64_t T);
 
 /* ------------------------------------------------------------------------
+ * AGCBank: a look-ahead hang AGC over the rows of a bank: float32 [C][K] (an
+ * SSBBank, AMBank or FMBank output read in place, an AudioBank's input) or,
+ * with cplx = 1, complex64 [C][K].  No reference counterpart (liquid's agc is a
+ * per-sample loop over one stream; ldsp_agc_* restates it); the definition is
+ * this library's own.  It is chosen so that the per-row recursion is an exact
+ * integer max-plus scan: every partition of a row's blocks gives the same bits.
+ * All level arithmetic is in integer units of 2^-24 octave of amplitude
+ * (Q = 2^24).  A dB value v becomes llrint(v Q / (20 log10 2)) in double: T
+ * (target, dB re amplitude 1), Gmax (max_gain) and d (decay per block).
+ * FLOOR = -64 Q, CEIL = +64 Q.  Levels are int32; the one product that leaves
+ * that range (blocks times d) is int64 and the result saturates at FLOOR.
+ * Per row c, for block b = 0, 1, .. of B samples of the row's stream x[t]
+ * (t counts from 0 since creation or reset):
+ *   a_b       = the largest |x[t]| of the block over its finite samples (a NaN
+ *               or Inf sample counts as 0).  Real rows: |x| as float32.  Complex
+ *               rows: the square root, in double, of the largest re re + im im
+ *               taken in double (the products are exact there: one rounding).
+ *   peak_q[b] = clamp(ceil(log2(a_b) Q), FLOOR, CEIL), FLOOR for a_b = 0; log2 in
+ *               double, once per block
+ *   w_b       = max(peak_q[b - H .. b])              blocks before 0: FLOOR
+ *   L_b       = max(w_b, L_{b-1} - d, FLOOR),  L_{-1} = FLOOR
+ *             = max(FLOOR, max_{j <= b} (peak_q[j] - d max(0, b - j - H)))
+ *               instant attack, a hold of H blocks, then d per block
+ *   gain_q[b] = min(T - L_b, Gmax)
+ *   g_b       = (float) exp2(gain_q[b] / Q)          exp2 in double, once per block
+ *   h_b       = min(g_b, g_{b+1}),  h_{-1} = g_0     boundary gains: one block of look-ahead
+ *   y[bB + i] = x[bB + i] gamma,  gamma = h_{b-1} + (h_b - h_{b-1}) (i + 1) / B
+ *               in float32, evaluated left to right, i = 0 .. B - 1
+ * So gamma <= g_b everywhere in block b and |y| <= target up to float32
+ * rounding; the gain ramps and never steps.  A non-finite input sample comes
+ * out non-finite at its own position and nowhere else; a row of zeros comes out
+ * as zeros at max_gain.  gain_q is an exact function of the peak_q returned.
+ * Block b is tracked (peak_q, gain_q) by the call that delivers its last sample
+ * and emitted by the call that delivers the last sample of block b + 1: after T
+ * samples T / B blocks are tracked and max(0, T / B - 1) emitted.  A call returns
+ * the difference of each count; output sample t lines up with input sample t.
+ * K = 0 and calls too short for a block are allowed and carry state only.  The
+ * object carries per row the up to 2B - 1 samples not yet emitted, the last H
+ * quantised peaks, the tracker level and the two boundary gains in flight.  A
+ * row's bits (y, peak_q, gain_q) depend neither on how the stream is cut into
+ * calls, nor on the other rows, their number or order, nor on the row strides.
+ *   1 <= C <= 256;  16 <= B <= 4096 (any integer);  0 <= H <= 255 blocks;
+ *   decay >= 0 dB per block (from 128 octaves per block on it acts as that);
+ *   |target| and |max_gain| <= 180 dB;  ntarget = 1 (every row) or C.
+ * Anything else (a NaN among them) is LDSP_EINVAL.  Everything is fixed at
+ * creation.
+ * ldsp_agcbank_execute reads row c at x + c * ldx (samples, ldx >= K) and writes
+ * row c of the emitted samples to y + c * ldy (samples) and of peak_q and gain_q
+ * to peak_q + c * ldq and gain_q + c * ldq (int32).  It sets *nw to the samples
+ * written per row and, when ldy < *nw or ldq < the tracked blocks, returns
+ * LDSP_ERANGE without consuming the input.  Argument errors are decided on the
+ * host before any device work.
+ * ldsp_agcbank_get_state copies out, per row, the tracker level, the last H
+ * peaks (oldest first) and the two boundary gains (h before the pending block,
+ * the pending block's g; 0 before the first block) after the last call; it
+ * waits for that call.
+ * Not built: a target setter, a flush of the last blocks, a measure-only call,
+ * an RMS detector, a per-row block / hang / decay, a sample-rate-aware time
+ * constant, skipping closed rows, any change of ldsp_agc_*.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_agcbank_s *ldsp_agcbank_t;
+int ldsp_agcbank_create(unsigned int C, unsigned int B, const double *target_dB, unsigned int ntarget, double max_gain_dB,
+                        unsigned int hang, double decay_dB, int cplx, ldsp_agcbank_t *q);
+int ldsp_agcbank_destroy(ldsp_agcbank_t q);
+int ldsp_agcbank_reset(ldsp_agcbank_t q);
+/* Any pointer may be NULL.  target_dB: C doubles.  fill: samples per row carried to the next call. */
+int ldsp_agcbank_get_info(ldsp_agcbank_t q, unsigned int *C, unsigned int *B, unsigned int *hang, double *decay_dB,
+                          double *max_gain_dB, double *target_dB, int *cplx, unsigned int *fill);
+/* Blocks a call of K samples tracks and emits; either pointer may be NULL, not both. */
+int ldsp_agcbank_num_outputs(ldsp_agcbank_t q, size_t K, size_t *tracked, size_t *emitted);
+int ldsp_agcbank_execute(ldsp_agcbank_t q, const void *x, size_t ldx, size_t K, void *y, size_t ldy, int32_t *peak_q,
+                         int32_t *gain_q, size_t ldq, size_t *nw, int mem, void *stream);
+/* Any pointer may be NULL.  level: C;  peaks: C * H;  gains: C * 2. */
+int ldsp_agcbank_get_state(ldsp_agcbank_t q, int32_t *level, int32_t *peaks, float *gains);
+/* Test hooks: dB to units;  the tracker on the host: L[i] for n new peaks in
+ * partitions of `width` blocks, from *level (updated) and the `hang` peaks
+ * before them (oldest first, updated), with the decay d in units. */
+int ldsp_debug_agcbank_units(double dB, int64_t *units);
+int ldsp_debug_agcbank_track(const int32_t *peak_q, size_t n, unsigned int hang, int64_t d, size_t width, int32_t *level,
+                             int32_t *peaks, int32_t *L);
+
+/* ------------------------------------------------------------------------
  * Spectrogram: a streaming Welch periodogram, one complex64 stream to rows of
  * power per bin and a running mean of them.  No reference counterpart
  * (liquid's spgramcf / spwaterfallcf are the same block: a zeroed window

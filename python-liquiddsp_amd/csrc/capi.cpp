@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "agc_track.hpp"
 #include "batch.hpp"
 #include "design.hpp"
 #include "modal.hpp"
@@ -1438,6 +1439,43 @@ struct ldsp_sqbank_s : ldsp::DevObj {
     void bind(int dev)
     {
         ldsp::upload(dthr, thr, dev);
+        zero_state(dev);
+    }
+};
+
+// AGCBank (look-ahead hang AGC over bank rows): the parameters in dB as given and
+// in the tracker's integer units, the host-side stream position (the blocks
+// tracked and emitted, the carried samples and the pending block follow from
+// it), and on the device the targets, per row the tracker level, the last H
+// peaks, the two boundary gains in flight, the samples not yet emitted as
+// [C][2B], ping-ponged, and the gains of one call.
+struct ldsp_agcbank_s : ldsp::DevObj {
+    unsigned int C = 0, B = 0, H = 0;
+    bool cplx = false;
+    double max_gain_db = 0.0, decay_db = 0.0;
+    std::vector<double> target_db;
+    std::vector<int32_t> T;
+    int32_t Gmax = 0;
+    int64_t d = 0;
+    uint64_t seen = 0;                     // input samples per row since create / reset
+    ldsp::DevBuf dtarget, dlevel, dtail, dedge, dgains;
+    ldsp::PingPong hist;
+    ldsp::Staging stg_peak, stg_gain;      // the other two outputs of a host-memory call (stg: x and y)
+    size_t esz() const { return cplx ? 8 : 4; }
+    uint64_t tracked(uint64_t s) const { return s / B; }
+    uint64_t emitted(uint64_t s) const { return s / B > 0 ? s / B - 1 : 0; }
+    size_t fill() const { return (size_t)(seen - emitted(seen) * B); }
+    int pend() const { return seen >= B ? 1 : 0; }
+    void zero_state(int dev)
+    {
+        ldsp::upload(dlevel, std::vector<int32_t>(C, ldsp::agc::kAgcFloor), dev);
+        ldsp::upload(dtail, std::vector<int32_t>((size_t)C * ldsp::k::kAgcbankTail, ldsp::agc::kAgcFloor), dev);
+        ldsp::upload(dedge, std::vector<float>((size_t)C * 2, 0.0f), dev);
+        hist.zero((size_t)C * 2 * B * esz(), dev);
+    }
+    void bind(int dev)
+    {
+        ldsp::upload(dtarget, T, dev);
         zero_state(dev);
     }
 };
@@ -4472,6 +4510,192 @@ int ldsp_debug_sqbank_tile(unsigned int B, size_t* blocks)
                      "sqbank: the block length must lie in " + std::to_string(k::kSqbankMinB) + " .. " +
                          std::to_string(k::kSqbankMaxB));
         *blocks = (size_t)k::sqbank_tile((int)B);
+    });
+}
+
+// ---------------------------------------------------------------- AGCBank
+// dB -> units of 2^-24 octave of amplitude: llrint(v 2^24 / (20 log10 2)) in double
+static int64_t agcbank_units(double dB) { return (int64_t)llrint(dB * agc::kAgcQ / (20.0 * log10(2.0))); }
+static const double kAgcbankMaxDb = 180.0;            // |target| and |max_gain|: within +-30 octaves
+int ldsp_agcbank_create(unsigned int C, unsigned int B, const double* target_dB, unsigned int ntarget, double max_gain_dB,
+                        unsigned int hang, double decay_dB, int cplx, ldsp_agcbank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(C >= 1 && C <= (unsigned)k::kAgcbankMaxC,
+                     "agcbank: the row count must lie in 1 .. " + std::to_string(k::kAgcbankMaxC));
+        LDSP_REQUIRE(B >= (unsigned)k::kAgcbankMinB && B <= (unsigned)k::kAgcbankMaxB,
+                     "agcbank: the block length must lie in " + std::to_string(k::kAgcbankMinB) + " .. " +
+                         std::to_string(k::kAgcbankMaxB));
+        LDSP_REQUIRE(hang <= (unsigned)agc::kAgcMaxHang,
+                     "agcbank: the hang must lie in 0 .. " + std::to_string(agc::kAgcMaxHang) + " blocks");
+        LDSP_REQUIRE(std::isfinite(decay_dB) && decay_dB >= 0.0, "agcbank: the decay must be at or above 0 dB per block");
+        LDSP_REQUIRE(std::isfinite(max_gain_dB) && std::fabs(max_gain_dB) <= kAgcbankMaxDb,
+                     "agcbank: max_gain must lie within +-180 dB");
+        LDSP_REQUIRE(cplx == 0 || cplx == 1, "agcbank: cplx must be 0 or 1");
+        NONNULL(target_dB);
+        LDSP_REQUIRE(ntarget == 1 || ntarget == C, "agcbank: one target or one per row");
+        for (unsigned i = 0; i < ntarget; i++)
+            LDSP_REQUIRE(std::isfinite(target_dB[i]) && std::fabs(target_dB[i]) <= kAgcbankMaxDb,
+                         "agcbank: targets must lie within +-180 dB");
+        std::unique_ptr<ldsp_agcbank_s> o(new ldsp_agcbank_s());
+        o->C = C;
+        o->B = B;
+        o->H = hang;
+        o->cplx = cplx != 0;
+        o->max_gain_db = max_gain_dB;
+        o->decay_db = decay_dB;
+        o->Gmax = (int32_t)agcbank_units(max_gain_dB);
+        // a decay of the whole range per block or more acts as the whole range
+        o->d = decay_dB >= 800.0 ? (int64_t)1 << 31 : std::min<int64_t>(agcbank_units(decay_dB), (int64_t)1 << 31);
+        o->target_db.resize(C);
+        o->T.resize(C);
+        for (unsigned c = 0; c < C; c++) {
+            o->target_db[c] = target_dB[ntarget == 1 ? 0 : c];
+            o->T[c] = (int32_t)agcbank_units(o->target_db[c]);
+        }
+        *q = o.release();
+    });
+}
+int ldsp_agcbank_destroy(ldsp_agcbank_t q) { return guard([&] { destroy(q); }); }
+int ldsp_agcbank_reset(ldsp_agcbank_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        q->seen = 0;
+        q->at_rest([&] { q->zero_state(q->device); });
+    });
+}
+int ldsp_agcbank_get_info(ldsp_agcbank_t q, unsigned int* C, unsigned int* B, unsigned int* hang, double* decay_dB,
+                          double* max_gain_dB, double* target_dB, int* cplx, unsigned int* fill)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (C) *C = q->C;
+        if (B) *B = q->B;
+        if (hang) *hang = q->H;
+        if (decay_dB) *decay_dB = q->decay_db;
+        if (max_gain_dB) *max_gain_dB = q->max_gain_db;
+        if (target_dB) std::copy(q->target_db.begin(), q->target_db.end(), target_dB);
+        if (cplx) *cplx = q->cplx ? 1 : 0;
+        if (fill) *fill = (unsigned)q->fill();
+    });
+}
+int ldsp_agcbank_num_outputs(ldsp_agcbank_t q, size_t K, size_t* tracked, size_t* emitted)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(tracked || emitted, "agcbank_num_outputs: tracked and emitted are both NULL");
+        if (tracked) *tracked = (size_t)(q->tracked(q->seen + K) - q->tracked(q->seen));
+        if (emitted) *emitted = (size_t)(q->emitted(q->seen + K) - q->emitted(q->seen));
+    });
+}
+int ldsp_agcbank_execute(ldsp_agcbank_t q, const void* x, size_t ldx, size_t K, void* y, size_t ldy, int32_t* peak_q,
+                         int32_t* gain_q, size_t ldq, size_t* nw, int mem, void* stream)
+{
+    LDSP_RANGE("ldsp_agcbank_execute");
+    return guard([&] {
+        NONNULL(q);
+        const size_t B = q->B, esz = q->esz();
+        const size_t nt = (size_t)(q->tracked(q->seen + K) - q->tracked(q->seen));
+        const size_t ne = (size_t)(q->emitted(q->seen + K) - q->emitted(q->seen));
+        if (nw) *nw = ne * B;
+        LDSP_REQUIRE(ldx >= K, "agcbank_execute: input row stride below the number of samples");
+        if (ne * B > ldy) throw Error(LDSP_ERANGE, "agcbank_execute: output row stride below the emitted samples");
+        if (nt > ldq) throw Error(LDSP_ERANGE, "agcbank_execute: peak_q / gain_q row stride below the tracked blocks");
+        LDSP_REQUIRE(K == 0 || x, "agcbank_execute: NULL input");
+        LDSP_REQUIRE(ne == 0 || y, "agcbank_execute: NULL output");
+        LDSP_REQUIRE(nt == 0 || (peak_q && gain_q), "agcbank_execute: NULL peak_q or gain_q");
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
+        const size_t C = q->C;
+        // a host-memory call reads and writes dense device images (rows of the caller's
+        // images are ldx, ldy and ldq elements apart)
+        const void* dx = q->stg.dev_in(e, x, K * esz, C, ldx * esz);
+        void* dy = q->stg.dev_out(e, y, C * ne * B * esz);
+        int32_t* dpq = (int32_t*)q->stg_peak.dev_out(e, peak_q, C * nt * 4);
+        int32_t* dgq = (int32_t*)q->stg_gain.dev_out(e, gain_q, C * nt * 4);
+        if (K > 0) {
+            k::AgcbankCall c;
+            c.x = dx;
+            c.hist = q->hist.in();
+            c.hist_out = q->hist.out();
+            c.n = K;
+            c.ldx = e.host ? K : ldx;
+            c.fill = q->fill();
+            c.pend = q->pend();
+            c.nt = nt;
+            c.ne = ne;
+            c.ldq = e.host ? nt : ldq;
+            c.ldg = nt + 2;
+            c.ldy = e.host ? ne * B : ldy;
+            c.C = (int)C;
+            c.B = (int)B;
+            c.H = (int)q->H;
+            c.cplx = q->cplx ? 1 : 0;
+            c.Gmax = q->Gmax;
+            c.d = q->d;
+            c.target = q->dtarget.as<int32_t>();
+            c.level = q->dlevel.as<int32_t>();
+            c.tail = q->dtail.as<int32_t>();
+            c.edge = q->dedge.as<float>();
+            c.peak_q = dpq;
+            c.gain_q = dgq;
+            c.gains = (float*)q->dgains.ensure(C * (nt + 2) * 4, e.device);
+            c.y = dy;
+            k::agcbank(c, e.stream);
+            q->hist.flip();
+            q->seen += K;
+        }
+        call.end();
+        q->stg.finish(e, y, ne * B * esz, C, ldy * esz);
+        q->stg_peak.finish(e, peak_q, nt * 4, C, ldq * 4);
+        q->stg_gain.finish(e, gain_q, nt * 4, C, ldq * 4);
+    });
+}
+int ldsp_agcbank_get_state(ldsp_agcbank_t q, int32_t* level, int32_t* peaks, float* gains)
+{
+    return guard([&] {
+        NONNULL(q);
+        const size_t C = q->C, H = q->H, TL = (size_t)k::kAgcbankTail;
+        std::vector<int32_t> lv(C, agc::kAgcFloor), tl(C * TL, agc::kAgcFloor);
+        std::vector<float> ed(C * 2, 0.0f);
+        q->at_rest([&] {
+            LDSP_HIP(hipMemcpy(lv.data(), q->dlevel.p, lv.size() * 4, hipMemcpyDeviceToHost));
+            LDSP_HIP(hipMemcpy(tl.data(), q->dtail.p, tl.size() * 4, hipMemcpyDeviceToHost));
+            LDSP_HIP(hipMemcpy(ed.data(), q->dedge.p, ed.size() * 4, hipMemcpyDeviceToHost));
+        });
+        if (level) std::copy(lv.begin(), lv.end(), level);
+        if (peaks)
+            for (size_t c = 0; c < C; c++) std::copy_n(&tl[c * TL + TL - H], H, peaks + c * H);
+        if (gains) std::copy(ed.begin(), ed.end(), gains);
+    });
+}
+int ldsp_debug_agcbank_units(double dB, int64_t* units)
+{
+    return guard([&] {
+        NONNULL(units);
+        LDSP_REQUIRE(std::isfinite(dB) && std::fabs(dB) <= 1.0e9, "agcbank: dB out of range");
+        *units = agcbank_units(dB);
+    });
+}
+int ldsp_debug_agcbank_track(const int32_t* peak_q, size_t n, unsigned int hang, int64_t d, size_t width, int32_t* level,
+                             int32_t* peaks, int32_t* L)
+{
+    return guard([&] {
+        NONNULL(level);
+        LDSP_REQUIRE(n == 0 || (peak_q && L), "agcbank_track: NULL peak_q or L");
+        LDSP_REQUIRE(hang <= (unsigned)agc::kAgcMaxHang, "agcbank_track: the hang must lie in 0 .. 255 blocks");
+        LDSP_REQUIRE(hang == 0 || peaks, "agcbank_track: NULL peaks");
+        LDSP_REQUIRE(d >= 0 && d <= ((int64_t)1 << 31), "agcbank_track: the decay must lie in 0 .. 2^31 units");
+        LDSP_REQUIRE(width >= 1, "agcbank_track: the partition width must be at least 1");
+        LDSP_REQUIRE(n <= ((size_t)1 << 31), "agcbank_track: too many blocks");
+        auto in_range = [](int32_t v) { return v >= agc::kAgcFloor && v <= agc::kAgcCeil; };
+        LDSP_REQUIRE(in_range(*level), "agcbank_track: level out of range");
+        for (unsigned i = 0; i < hang; i++) LDSP_REQUIRE(in_range(peaks[i]), "agcbank_track: peaks out of range");
+        for (size_t i = 0; i < n; i++) LDSP_REQUIRE(in_range(peak_q[i]), "agcbank_track: peak_q out of range");
+        if (n == 0) return;
+        agc::agc_track_partitioned(peak_q, n, hang, d, width, level, peaks, L);
     });
 }
 

@@ -530,6 +530,44 @@ struct SqbankCall {
     void* y;
 };
 void sqbank(const SqbankCall& c, hipStream_t s);
+// k_agcbank.hip: look-ahead hang AGC over bank rows (AGCBank).  C <= kAgcbankMaxC
+// rows of float32 or (cplx) complex64, row c's n samples at x + c * ldx; blocks of
+// kAgcbankMinB <= B <= kAgcbankMaxB samples.  The call's stream per row is the
+// fill < 2B carried samples (hist, [C][2B]) followed by x: the samples not yet
+// emitted, whose first B are the block tracked last when pend = 1.  The call
+// tracks the nt = (fill + n - pend B) / B blocks after that one and emits the
+// ne = max(pend + nt - 1, 0) blocks from the stream's start; hist_out (a distinct
+// buffer) receives the fill + n - ne B samples after them.  peak_q[c * ldq + b]
+// and gain_q[c * ldq + b], b < nt, receive row c; gains ([C][ldg], ldg >=
+// pend + nt + 1) is scratch for the boundary gain before the call and the
+// blocks' g; y receives ne B samples per row at y + c * ldy.  Per row, updated in
+// place: level (the tracker), tail ([C][256], the last H peaks, newest last) and
+// edge ([C][2]: the boundary gain before the pending block, the pending block's
+// g).  target: per row, units; Gmax and d: units (agc_track.hpp).  n = 0 launches
+// nothing.
+constexpr int kAgcbankMaxC = 256;
+constexpr int kAgcbankMinB = 16;
+constexpr int kAgcbankMaxB = 4096;
+constexpr int kAgcbankTail = 256;
+int agcbank_tile(int B, int cplx);                          // blocks per workgroup of k_agcbank_peak / _apply
+struct AgcbankCall {
+    const void* x;
+    const void* hist;
+    void* hist_out;
+    size_t n, ldx, fill, nt, ne, ldq, ldg, ldy;
+    int C, B, H, pend, cplx;
+    int32_t Gmax;
+    int64_t d;
+    const int32_t* target;
+    int32_t* level;
+    int32_t* tail;
+    float* edge;
+    int32_t* peak_q;
+    int32_t* gain_q;
+    float* gains;
+    void* y;
+};
+void agcbank(const AgcbankCall& c, hipStream_t s);
 // k_stbank.hip: FM stereo decoder over bank rows (StereoBank).  C <= kStbankMaxC
 // rows of float32 multiplex, row c's n samples at x + c * ldx; decimation
 // 1 <= D <= kStbankMaxD, two real prototypes of L <= kStbankMaxL taps.  hist /

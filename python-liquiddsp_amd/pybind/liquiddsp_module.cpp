@@ -94,15 +94,21 @@ T get_value(G get, const Q& q)
 }
 
 // The element kinds of inputs and results
-enum class Kind { f32, c64, i16, u8 };
+enum class Kind { f32, c64, i16, u8, i32 };
 constexpr Kind kind_of(bool cplx) { return cplx ? Kind::c64 : Kind::f32; }
 const char* torch_name(Kind k)
 {
+    if (k == Kind::i32) return "int32";
     return k == Kind::c64 ? "complex64" : (k == Kind::f32 ? "float32" : (k == Kind::i16 ? "int16" : "uint8"));
 }
-size_t kind_size(Kind k) { return k == Kind::c64 ? 8 : (k == Kind::f32 ? 4 : (k == Kind::i16 ? 2 : 1)); }
+size_t kind_size(Kind k)
+{
+    if (k == Kind::i32) return 4;
+    return k == Kind::c64 ? 8 : (k == Kind::f32 ? 4 : (k == Kind::i16 ? 2 : 1));
+}
 py::dtype np_dtype(Kind k)
 {
+    if (k == Kind::i32) return py::dtype::of<int32_t>();
     return k == Kind::c64 ? py::dtype::of<cf>()
                           : (k == Kind::f32 ? py::dtype::of<float>()
                                             : (k == Kind::i16 ? py::dtype::of<int16_t>() : py::dtype::of<uint8_t>()));
@@ -1262,6 +1268,81 @@ struct SquelchBank {
     py::object measure(const py::handle& x) { return run(x, false); }
 };
 
+// ------------------------------------------------------------------ AGCBank (no reference counterpart; AGC restates liquid's loop)
+// Look-ahead hang AGC over bank rows (ldsp.h): float32[nchan, K] (input as the
+// AudioBank's: a bank's output is read in place) or complex64[nchan, K] ->
+// the emitted blocks, the same kind.  peak_q, gain_q and gain_db keep the last
+// call's tracked blocks.
+struct AGCBank {
+    Handle<ldsp_agcbank_t, ldsp_agcbank_destroy> q;
+    unsigned C = 0, B = 0, H = 0;
+    double decay = 0.0, max_gain = 0.0;
+    bool cplx = false;
+    py::object last_peak = py::none(), last_gain = py::none();
+    AGCBank(int nchan, int block, const py::object& target, double max_gain_, int hang, double decay_, bool complex_)
+    {
+        if (nchan < 0) throw py::value_error("AGCBank: nchan must lie in 1 .. 256");
+        if (block < 0) throw py::value_error("AGCBank: block must lie in 16 .. 4096");
+        if (hang < 0) throw py::value_error("AGCBank: hang must lie in 0 .. 255");
+        const std::vector<double> t = SquelchBank::to_dvec(target);
+        if (t.empty()) throw py::value_error("AGCBank: one target or one per row");
+        check(ldsp_agcbank_create((unsigned)nchan, (unsigned)block, t.data(), (unsigned)t.size(), max_gain_, (unsigned)hang,
+                                  decay_, complex_ ? 1 : 0, q.out()));
+        int cx = 0;
+        check(ldsp_agcbank_get_info(q, &C, &B, &H, &decay, &max_gain, nullptr, &cx, nullptr));
+        cplx = cx != 0;
+    }
+    void reset() { check(ldsp_agcbank_reset(q)); }
+    py::array_t<double> target()
+    {
+        py::array_t<double> t(C);
+        check(ldsp_agcbank_get_info(q, nullptr, nullptr, nullptr, nullptr, nullptr, t.mutable_data(), nullptr, nullptr));
+        return t;
+    }
+    unsigned fill()
+    {
+        unsigned f;
+        check(ldsp_agcbank_get_info(q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &f));
+        return f;
+    }
+    size_t num_outputs(size_t K)
+    {
+        size_t ne;
+        check(ldsp_agcbank_num_outputs(q, K, nullptr, &ne));
+        return ne * B;
+    }
+    py::tuple state()
+    {
+        py::array_t<int32_t> level(C), peaks({(py::ssize_t)C, (py::ssize_t)H});
+        py::array_t<float> gains({(py::ssize_t)C, (py::ssize_t)2});
+        check(ldsp_agcbank_get_state(q, level.mutable_data(), peaks.mutable_data(), gains.mutable_data()));
+        return py::make_tuple(level, peaks, gains);
+    }
+    py::object gain_db()
+    {
+        if (last_gain.is_none()) return py::none();
+        const double c = 20.0 * std::log10(2.0) / 16777216.0;   // dB per unit
+        if (is_device_tensor(last_gain)) return last_gain.attr("double")().attr("mul")(c).attr("float")();
+        return last_gain.attr("astype")("float64").attr("__mul__")(c).attr("astype")("float32");
+    }
+    py::object call(const py::handle& x)
+    {
+        const Kind kd = kind_of(cplx);
+        const CallIn in = in_rows(x, kd, C, "AGCBank", true, Strided::refuse);
+        size_t nt = 0, ne = 0, nw = 0;
+        check(ldsp_agcbank_num_outputs(q, in.n, &nt, &ne));
+        CallOut y = make_out(in, kd, C, (py::ssize_t)(ne * B)), pq = make_out(in, Kind::i32, C, (py::ssize_t)nt),
+                gq = make_out(in, Kind::i32, C, (py::ssize_t)nt);
+        invoke(in, [&](int mem, void* s) {
+            return ldsp_agcbank_execute(q, in.ptr, in.ld, in.n, y.ptr, ne * B, (int32_t*)pq.ptr, (int32_t*)gq.ptr, nt, &nw,
+                                        mem, s);
+        });
+        last_peak = pq.obj;
+        last_gain = gq.obj;
+        return y.obj;
+    }
+};
+
 // ------------------------------------------------------------------ StereoBank (no reference counterpart; FMStereo is another decoder)
 // Feed-forward FM stereo decoder over bank rows (ldsp.h): float32[nchan, K] of
 // multiplex -> float32[nchan, 2, ncols], left at [:, 0] and right at [:, 1]; its
@@ -2404,6 +2485,32 @@ PYBIND11_MODULE(_liquiddsp, m)
              "complex64[nchan, K] -> (status, level); advances the stream, writes no rows")
         .def("__call__", &SquelchBank::call,
              "complex64[nchan, K] -> complex64[nchan, nblocks * block]: the stream's whole blocks, closed ones zeroed");
+
+    // ---- AGCBank (beyond the reference: look-ahead hang AGC over bank rows)
+    py::class_<AGCBank>(m, "AGCBank")
+        .def(py::init<int, int, py::object, double, int, double, bool>(), py::arg("nchan"), py::arg("block") = 256,
+             py::arg("target") = -12.0, py::arg("max_gain") = 60.0, py::arg("hang") = 8, py::arg("decay") = 0.5,
+             py::arg("complex") = false)
+        .def("reset", &AGCBank::reset, "the initial state")
+        .def("num_outputs", &AGCBank::num_outputs, py::arg("K"),
+             "samples per row the next call returns for K input samples per row")
+        .def_property_readonly("nchan", [](AGCBank& c) { return c.C; })
+        .def_property_readonly("block", [](AGCBank& c) { return c.B; })
+        .def_property_readonly("hang", [](AGCBank& c) { return c.H; }, "in blocks")
+        .def_property_readonly("decay", [](AGCBank& c) { return c.decay; }, "dB per block")
+        .def_property_readonly("max_gain", [](AGCBank& c) { return c.max_gain; }, "dB")
+        .def_property_readonly("complex", [](AGCBank& c) { return c.cplx; })
+        .def_property_readonly("target", &AGCBank::target, "dB re amplitude 1, per row")
+        .def_property_readonly("fill", &AGCBank::fill, "samples per row carried to the next call")
+        .def_property_readonly("state", &AGCBank::state,
+                               "(level, the last hang peaks, the two boundary gains) per row after the last call")
+        .def_property_readonly("peak_q", [](AGCBank& c) { return c.last_peak; },
+                               "the last call's int32[nchan, tracked], units of 2^-24 octave; None before the first")
+        .def_property_readonly("gain_q", [](AGCBank& c) { return c.last_gain; },
+                               "the last call's int32[nchan, tracked], units of 2^-24 octave; None before the first")
+        .def_property_readonly("gain_db", &AGCBank::gain_db, "gain_q in dB, float32")
+        .def("__call__", &AGCBank::call,
+             "float32 or complex64 [nchan, K] -> the same kind [nchan, emitted * block]: the stream one block behind");
 
     // ---- StereoBank (beyond the reference: feed-forward FM stereo decoder over bank rows)
     py::class_<StereoBank>(m, "StereoBank")
