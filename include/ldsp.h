@@ -1202,6 +1202,97 @@ int ldsp_debug_agcbank_track(const int32_t *peak_q, size_t n, unsigned int hang,
                              int32_t *peaks, int32_t *L);
 
 /* ------------------------------------------------------------------------
+ * ToneBank: for every row of a float32 [C][K] block (an FMBank, AMBank, SSBBank
+ * or AGCBank output, read in place), the power at F listed tones per block of B
+ * samples, the dominant tone of the block and, optionally, the rows themselves
+ * with the blocks zeroed in which no accepted tone was heard lately: a CTCSS /
+ * tone-burst / paging-tone detector and tone squelch.  No reference counterpart;
+ * the definition is this library's own.  The F tones f_k (cycles per row sample)
+ * are common to all rows.  With the window w[i] = 0.5 - 0.5 cos(2 pi i / B)
+ * (HANN, periodic) or 1 (RECT) and s = sqrt(2) / sum_i w[i], the tables
+ *   Tc[k][i] = s w[i] cos(2 pi f_k i)      Ts[k][i] = -s w[i] sin(2 pi f_k i)
+ * are computed in double and each entry rounded once to float32; the phase
+ * restarts at every block and the kernel multiplies by nothing else.  For block
+ * b of row c of the concatenated input x[c][t] (t counted from 0 since creation
+ * or reset):
+ *   Xre = sum_{i<B} Tc[k][i] x[c][bB + i]   Xim = sum_{i<B} Ts[k][i] x[c][bB + i]
+ *   power[c][b][k] = fmaf(Xre, Xre, Xim * Xim)                          float32
+ * Xre and Xim are float32 values whose summation order is fixed by B alone:
+ * float32 fmaf chains over S = 16, 32, 64, 128, 256 samples each (from B = 64,
+ * 256, 1024, 4096, 16384 up), whose sums are added in float64 in a fixed order
+ * and rounded once to float32 (one chain over 192 samples measured 1.2e-6 of
+ * the largest power off, over 4096 samples 2.4e-6 emulated).  A sinusoid of
+ * amplitude A at f_k reads A^2 / 2.  Two tones closer than 2 / B cycles per
+ * sample (HANN; 1 / B for RECT) both respond to either.  The decision is an
+ * exact function of the float32 powers returned:
+ *   k* = the lowest index of the block's largest power
+ *   others = sum_{k != k*} (double) power[k], added in index order
+ *   hit = every power of the block is finite
+ *         and power[k*] > floor                              (in float32)
+ *         and (double) power[k*] (F - 1) > dominance others  (in float64)
+ *   tone[c][b] = hit ? k* : -1                                             int8
+ *   accepted = hit and (want[c] < 0 or want[c] == k*)
+ *   open[c][b] = some block in [b - hold, b] of the row's stream was accepted
+ *                (blocks before the stream's start were not)        uint8, 0 / 1
+ *   y[c][bB + i] = open ? x[c][bB + i] (the same bits) : +0.0
+ * The compares are strict: a block of zeros is never a hit.  dominance is the
+ * ratio of the best power to the mean of the others.
+ * Block b is emitted by the call that delivers its last sample, as the
+ * SquelchBank's: with T samples per row seen before a call, a call of K samples
+ * returns (T + K) / B - T / B blocks; K = 0 and calls too short for a block carry
+ * state only; the fill = (T + K) mod B samples of the unfinished block are
+ * carried, and the gated output of a call is float32 [C][nblocks B].  Per-row
+ * state is the carried samples and one integer, the blocks since the last
+ * accepted one, which saturates at 65.  A row's bits (power, tone, open, gated
+ * samples) depend neither on how the stream is cut into calls, nor on the other
+ * rows, their number or order, nor on the row strides.
+ *   1 <= C <= 256;  2 <= F <= 64;  0 < f_k < 0.5, finite;  B a multiple of 64,
+ *   64 <= B <= 16384;  window LDSP_TONE_RECT or LDSP_TONE_HANN;  dominance >= 1;
+ *   floor >= 0;  0 <= hold <= 64;  -1 <= want[c] <= F - 1 (-1: any listed tone).
+ * Anything else (a NaN among them) is LDSP_EINVAL.  Argument errors are decided
+ * on the host before any device work.
+ * ldsp_tonebank_create sets want = -1 for every row.  ldsp_tonebank_set_want
+ * takes n = 1 (every row) or n = C values; it, ldsp_tonebank_set_dominance and
+ * ldsp_tonebank_set_floor take effect at the next block and touch no state;
+ * ldsp_tonebank_reset restores the initial state and keeps the settings.
+ * ldsp_tonebank_execute reads row c at x + c * ldx (ldx >= K) and writes row c
+ * of power to power + c * ldp (floats, [nblocks][F]), of tone to tone + c * ldt,
+ * of open to open + c * ldo (bytes; open may be NULL) and, where y is not NULL,
+ * of the gated samples to y + c * ldy; with y == NULL it only measures.  It
+ * sets *nblocks and, when ldp < *nblocks F, ldt or ldo < *nblocks or ldy <
+ * *nblocks B, returns LDSP_ERANGE without consuming the input.
+ * ldsp_tonebank_get_state copies out, per row, the blocks since the last
+ * accepted one (65: none within reach); it waits for the last call.
+ * Not built: overlapping blocks, a look-ahead block (a transmission's first
+ * partial block stays closed), complex rows, per-row tone lists, blocks or
+ * thresholds, DTMF pair logic, code (DCS) squelch, skipping closed rows.
+ * ---------------------------------------------------------------------- */
+typedef struct ldsp_tonebank_s *ldsp_tonebank_t;
+enum { LDSP_TONE_RECT = 0, LDSP_TONE_HANN = 1 };
+int ldsp_tonebank_create(unsigned int C, const double *tones, unsigned int F, unsigned int B, int window,
+                         double dominance, float floor, unsigned int hold, ldsp_tonebank_t *q);
+int ldsp_tonebank_destroy(ldsp_tonebank_t q);
+int ldsp_tonebank_reset(ldsp_tonebank_t q);
+/* Any pointer may be NULL.  fill: samples per row carried to the next call. */
+int ldsp_tonebank_get_info(ldsp_tonebank_t q, unsigned int *C, unsigned int *F, unsigned int *B, int *window,
+                           unsigned int *hold, unsigned int *fill);
+/* Any pointer may be NULL.  tones: F;  tc, ts: F * B each, [k][i];  sumw: sum_i w[i] in double. */
+int ldsp_tonebank_get_tables(ldsp_tonebank_t q, double *tones, float *tc, float *ts, double *sumw);
+int ldsp_tonebank_set_want(ldsp_tonebank_t q, const int *want, unsigned int n);     /* n = 1 or C */
+int ldsp_tonebank_get_want(ldsp_tonebank_t q, int *want);                           /* C values */
+int ldsp_tonebank_set_dominance(ldsp_tonebank_t q, double dominance);
+int ldsp_tonebank_get_dominance(ldsp_tonebank_t q, double *dominance);
+int ldsp_tonebank_set_floor(ldsp_tonebank_t q, float floor);
+int ldsp_tonebank_get_floor(ldsp_tonebank_t q, float *floor);
+int ldsp_tonebank_num_outputs(ldsp_tonebank_t q, size_t K, size_t *nblocks);
+int ldsp_tonebank_execute(ldsp_tonebank_t q, const float *x, size_t ldx, size_t K, float *power, size_t ldp, int8_t *tone,
+                          size_t ldt, uint8_t *open, size_t ldo, float *y, size_t ldy, size_t *nblocks, int mem,
+                          void *stream);
+int ldsp_tonebank_get_state(ldsp_tonebank_t q, int *since);                         /* C values */
+/* Test hook: columns (row, block pairs) per workgroup of the power kernel. */
+int ldsp_debug_tonebank_tile(unsigned int B, size_t *columns);
+
+/* ------------------------------------------------------------------------
  * Spectrogram: a streaming Welch periodogram, one complex64 stream to rows of
  * power per bin and a running mean of them.  No reference counterpart
  * (liquid's spgramcf / spwaterfallcf are the same block: a zeroed window

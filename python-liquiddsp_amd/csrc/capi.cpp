@@ -1480,6 +1480,43 @@ struct ldsp_agcbank_s : ldsp::DevObj {
     }
 };
 
+// ToneBank (per-row tone detector and tone squelch over bank rows): the tones and
+// the two tables as handed back, the settings, the host-side stream position
+// (fill and the block count of a call follow from it), and on the device the
+// tables in the power kernel's layout, the wanted tone per row, per row the
+// blocks since the last accepted one and the carried samples of the unfinished
+// block as [C][B], both ping-ponged, and the open flags of a call that passes none.
+struct ldsp_tonebank_s : ldsp::DevObj {
+    unsigned int C = 0, F = 0, B = 0, hold = 0;
+    int window = 0;
+    double dominance = 0.0, sumw = 0.0;
+    float floor = 0.0f;
+    std::vector<double> tones;
+    std::vector<float> tc, ts;             // [F][B] each
+    std::vector<int8_t> want;
+    uint64_t seen = 0;                     // input samples per row since create / reset
+    ldsp::DevBuf dtab, dwant, dopen;
+    ldsp::PingPong hist, since;
+    ldsp::Staging stg_power, stg_tone, stg_open;   // the other outputs of a host-memory call (stg: x and y)
+    size_t fill() const { return (size_t)(seen % B); }
+    size_t num_outputs(size_t K) const { return (size_t)((seen + K) / B - seen / B); }
+    void zero_state(int dev)
+    {
+        hist.zero((size_t)C * B * 4, dev);
+        const std::vector<int> none(C, ldsp::k::kTonebankSat);
+        for (auto& d : since.b) ldsp::upload(d, none, dev);
+        since.cur = 0;
+    }
+    void bind(int dev)
+    {
+        std::vector<float> t;
+        ldsp::k::tonebank_pack((int)F, (int)B, tc.data(), ts.data(), t);
+        ldsp::upload(dtab, t, dev);
+        ldsp::upload(dwant, want, dev);
+        zero_state(dev);
+    }
+};
+
 // StereoBank (FM stereo decoder over bank rows): the two prototypes, the pilot
 // word and threshold, the host-side stream position (skip follows from it), and
 // on the device the tap table in the kernel's layout (kernels.hpp), per row the
@@ -4696,6 +4733,249 @@ int ldsp_debug_agcbank_track(const int32_t* peak_q, size_t n, unsigned int hang,
         for (size_t i = 0; i < n; i++) LDSP_REQUIRE(in_range(peak_q[i]), "agcbank_track: peak_q out of range");
         if (n == 0) return;
         agc::agc_track_partitioned(peak_q, n, hang, d, width, level, peaks, L);
+    });
+}
+
+// ---------------------------------------------------------------- ToneBank
+static std::string tonebank_block_text()
+{
+    return "tonebank: the block length must be a multiple of 64 in " + std::to_string(k::kTonebankMinB) + " .. " +
+           std::to_string(k::kTonebankMaxB);
+}
+static void tonebank_want(const int* want, unsigned int n, unsigned int C, unsigned int F, std::vector<int8_t>& out)
+{
+    NONNULL(want);
+    LDSP_REQUIRE(n == 1 || n == C, "tonebank: one wanted tone or one per row");
+    for (unsigned i = 0; i < n; i++)
+        LDSP_REQUIRE(want[i] >= -1 && want[i] < (int)F, "tonebank: want must lie in -1 .. F - 1");
+    out.resize(C);
+    for (unsigned c = 0; c < C; c++) out[c] = (int8_t)want[n == 1 ? 0 : c];
+}
+int ldsp_tonebank_create(unsigned int C, const double* tones, unsigned int F, unsigned int B, int window, double dominance,
+                         float floor, unsigned int hold, ldsp_tonebank_t* q)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(C >= 1 && C <= (unsigned)k::kTonebankMaxC,
+                     "tonebank: the row count must lie in 1 .. " + std::to_string(k::kTonebankMaxC));
+        LDSP_REQUIRE(F >= (unsigned)k::kTonebankMinF && F <= (unsigned)k::kTonebankMaxF,
+                     "tonebank: the number of tones must lie in " + std::to_string(k::kTonebankMinF) + " .. " +
+                         std::to_string(k::kTonebankMaxF));
+        NONNULL(tones);
+        for (unsigned i = 0; i < F; i++)
+            LDSP_REQUIRE(std::isfinite(tones[i]) && tones[i] > 0.0 && tones[i] < 0.5,
+                         "tonebank: tones must lie in (0, 0.5) cycles per sample");
+        LDSP_REQUIRE(B >= (unsigned)k::kTonebankMinB && B <= (unsigned)k::kTonebankMaxB && B % 64 == 0,
+                     tonebank_block_text());
+        LDSP_REQUIRE(window == LDSP_TONE_RECT || window == LDSP_TONE_HANN, "tonebank: unknown window");
+        LDSP_REQUIRE(dominance >= 1.0 && std::isfinite(dominance), "tonebank: the dominance must be finite and >= 1");
+        LDSP_REQUIRE(floor >= 0.0f && std::isfinite(floor), "tonebank: the floor must be finite and >= 0");
+        LDSP_REQUIRE(hold <= (unsigned)k::kTonebankMaxHold,
+                     "tonebank: the hold must lie in 0 .. " + std::to_string(k::kTonebankMaxHold) + " blocks");
+        std::unique_ptr<ldsp_tonebank_s> o(new ldsp_tonebank_s());
+        o->C = C;
+        o->F = F;
+        o->B = B;
+        o->window = window;
+        o->dominance = dominance;
+        o->floor = floor;
+        o->hold = hold;
+        o->tones.assign(tones, tones + F);
+        o->want.assign(C, (int8_t)-1);
+        // the tables in double, each entry rounded once
+        const double two_pi = 2.0 * M_PI;
+        std::vector<double> w(B, 1.0);
+        if (window == LDSP_TONE_HANN)
+            for (unsigned i = 0; i < B; i++) w[i] = 0.5 - 0.5 * cos(two_pi * (double)i / (double)B);
+        double sum = 0.0;
+        for (unsigned i = 0; i < B; i++) sum += w[i];
+        o->sumw = sum;
+        const double s = sqrt(2.0) / sum;
+        o->tc.resize((size_t)F * B);
+        o->ts.resize((size_t)F * B);
+        for (unsigned kk = 0; kk < F; kk++)
+            for (unsigned i = 0; i < B; i++) {
+                const double ph = two_pi * tones[kk] * (double)i;
+                o->tc[(size_t)kk * B + i] = (float)(s * w[i] * cos(ph));
+                o->ts[(size_t)kk * B + i] = (float)(-s * w[i] * sin(ph));
+            }
+        *q = o.release();
+    });
+}
+int ldsp_tonebank_destroy(ldsp_tonebank_t q) { return guard([&] { destroy(q); }); }
+int ldsp_tonebank_reset(ldsp_tonebank_t q)
+{
+    return guard([&] {
+        NONNULL(q);
+        q->seen = 0;
+        q->at_rest([&] { q->zero_state(q->device); });
+    });
+}
+int ldsp_tonebank_get_info(ldsp_tonebank_t q, unsigned int* C, unsigned int* F, unsigned int* B, int* window,
+                           unsigned int* hold, unsigned int* fill)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (C) *C = q->C;
+        if (F) *F = q->F;
+        if (B) *B = q->B;
+        if (window) *window = q->window;
+        if (hold) *hold = q->hold;
+        if (fill) *fill = (unsigned)q->fill();
+    });
+}
+int ldsp_tonebank_get_tables(ldsp_tonebank_t q, double* tones, float* tc, float* ts, double* sumw)
+{
+    return guard([&] {
+        NONNULL(q);
+        if (tones) std::copy(q->tones.begin(), q->tones.end(), tones);
+        if (tc) std::copy(q->tc.begin(), q->tc.end(), tc);
+        if (ts) std::copy(q->ts.begin(), q->ts.end(), ts);
+        if (sumw) *sumw = q->sumw;
+    });
+}
+int ldsp_tonebank_set_want(ldsp_tonebank_t q, const int* want, unsigned int n)
+{
+    return guard([&] {
+        NONNULL(q);
+        std::vector<int8_t> w;
+        tonebank_want(want, n, q->C, q->F, w);
+        // the table changes only once the object's earlier calls have finished with it
+        q->at_rest([&] { ldsp::upload(q->dwant, w, q->device); });
+        q->want = std::move(w);
+    });
+}
+int ldsp_tonebank_get_want(ldsp_tonebank_t q, int* want)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(want);
+        std::copy(q->want.begin(), q->want.end(), want);
+    });
+}
+int ldsp_tonebank_set_dominance(ldsp_tonebank_t q, double dominance)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(dominance >= 1.0 && std::isfinite(dominance), "tonebank: the dominance must be finite and >= 1");
+        q->dominance = dominance;
+    });
+}
+int ldsp_tonebank_get_dominance(ldsp_tonebank_t q, double* dominance)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(dominance);
+        *dominance = q->dominance;
+    });
+}
+int ldsp_tonebank_set_floor(ldsp_tonebank_t q, float floor)
+{
+    return guard([&] {
+        NONNULL(q);
+        LDSP_REQUIRE(floor >= 0.0f && std::isfinite(floor), "tonebank: the floor must be finite and >= 0");
+        q->floor = floor;
+    });
+}
+int ldsp_tonebank_get_floor(ldsp_tonebank_t q, float* floor)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(floor);
+        *floor = q->floor;
+    });
+}
+int ldsp_tonebank_num_outputs(ldsp_tonebank_t q, size_t K, size_t* nblocks)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(nblocks);
+        *nblocks = q->num_outputs(K);
+    });
+}
+int ldsp_tonebank_execute(ldsp_tonebank_t q, const float* x, size_t ldx, size_t K, float* power, size_t ldp, int8_t* tone,
+                          size_t ldt, uint8_t* open, size_t ldo, float* y, size_t ldy, size_t* nblocks, int mem,
+                          void* stream)
+{
+    LDSP_RANGE("ldsp_tonebank_execute");
+    return guard([&] {
+        NONNULL(q);
+        const size_t N = q->num_outputs(K), B = q->B, F = q->F;
+        if (nblocks) *nblocks = N;
+        LDSP_REQUIRE(ldx >= K, "tonebank_execute: input row stride below the number of samples");
+        if (N * F > ldp) throw Error(LDSP_ERANGE, "tonebank_execute: power row stride below the blocks' tones");
+        if (N > ldt || (open && N > ldo))
+            throw Error(LDSP_ERANGE, "tonebank_execute: tone or open row stride below the number of blocks");
+        if (y && N * B > ldy) throw Error(LDSP_ERANGE, "tonebank_execute: output row stride below the blocks' samples");
+        LDSP_REQUIRE(K == 0 || x, "tonebank_execute: NULL input");
+        LDSP_REQUIRE(N == 0 || (power && tone), "tonebank_execute: NULL power or tone");
+        Call call(*q, mem, x, stream);
+        const Exec& e = call.e;
+        const size_t C = q->C;
+        // a host-memory call reads and writes dense device images (rows of the caller's
+        // images are ldx, ldp, ldt, ldo and ldy elements apart)
+        const void* dx = q->stg.dev_in(e, x, K * 4, C, ldx * 4);
+        float* dpow = (float*)q->stg_power.dev_out(e, power, C * N * F * 4);
+        int8_t* dtone = (int8_t*)q->stg_tone.dev_out(e, tone, C * N);
+        uint8_t* dopen = open ? (uint8_t*)q->stg_open.dev_out(e, open, C * N) : nullptr;
+        void* dy = y ? q->stg.dev_out(e, y, C * N * B * 4) : nullptr;
+        if (K > 0) {
+            k::TonebankCall c;
+            c.x = (const float*)dx;
+            c.hist = (const float*)q->hist.in();
+            c.hist_out = (float*)q->hist.out();
+            c.tab = q->dtab.as<float>();
+            c.n = K;
+            c.ldx = e.host ? K : ldx;
+            c.fill = q->fill();
+            c.nblocks = N;
+            c.ldp = e.host ? N * F : ldp;
+            c.ldt = e.host ? N : ldt;
+            c.ldo = e.host || !open ? N : ldo;
+            c.ldy = e.host ? N * B : ldy;
+            c.C = (int)C;
+            c.B = (int)B;
+            c.F = (int)F;
+            c.hold = (int)q->hold;
+            c.floor = q->floor;
+            c.dominance = q->dominance;
+            c.want = q->dwant.as<int8_t>();
+            c.since = (const int*)q->since.in();
+            c.since_out = (int*)q->since.out();
+            c.power = dpow;
+            c.tone = dtone;
+            // the gate reads the flags: a call that takes none keeps them in the object
+            c.open = dopen ? dopen : (uint8_t*)q->dopen.ensure(std::max<size_t>(C * N, 1), e.device);
+            c.y = (float*)dy;
+            k::tonebank(c, e.stream);
+            q->hist.flip();
+            if (N > 0) q->since.flip();
+            q->seen += K;
+        }
+        call.end();
+        q->stg_power.finish(e, power, N * F * 4, C, ldp * 4);
+        q->stg_tone.finish(e, tone, N, C, ldt);
+        if (open) q->stg_open.finish(e, open, N, C, ldo);
+        if (y) q->stg.finish(e, y, N * B * 4, C, ldy * 4);
+    });
+}
+int ldsp_tonebank_get_state(ldsp_tonebank_t q, int* since)
+{
+    return guard([&] {
+        NONNULL(q);
+        NONNULL(since);
+        std::vector<int> st(q->C, k::kTonebankSat);
+        q->at_rest([&] { LDSP_HIP(hipMemcpy(st.data(), q->since.in(), st.size() * sizeof(int), hipMemcpyDeviceToHost)); });
+        std::copy(st.begin(), st.end(), since);
+    });
+}
+int ldsp_debug_tonebank_tile(unsigned int B, size_t* columns)
+{
+    return guard([&] {
+        NONNULL(columns);
+        LDSP_REQUIRE(B >= (unsigned)k::kTonebankMinB && B <= (unsigned)k::kTonebankMaxB && B % 64 == 0,
+                     tonebank_block_text());
+        *columns = (size_t)k::tonebank_tile((int)B);
     });
 }
 

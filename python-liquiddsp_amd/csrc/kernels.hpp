@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace ldsp {
 namespace k {
@@ -568,6 +569,45 @@ struct AgcbankCall {
     void* y;
 };
 void agcbank(const AgcbankCall& c, hipStream_t s);
+// k_tonebank.hip: per-row tone detector and tone squelch over bank rows
+// (ToneBank).  C <= kTonebankMaxC rows of float32, row c's n samples at
+// x + c * ldx; blocks of B samples (a multiple of 64), F tones.  The call's
+// stream per row is the fill < B carried samples (hist, [C][B]) followed by x, as
+// k_sqbank.hip's; hist_out (a distinct buffer) receives the (fill + n) mod B
+// samples after the nblocks whole blocks.  tab: the tables in the power kernel's
+// layout (tonebank_pack, from tc and ts, [F][B] each).  power[c * ldp + b F + k],
+// tone[c * ldt + b] and open[c * ldo + b], b < nblocks, receive row c (none may
+// be NULL); y (may be NULL: the gate is not launched) receives nblocks B samples
+// per row at y + c * ldy.  want: per row;  since / since_out (distinct buffers):
+// per row the blocks since the last accepted one, at most kTonebankSat.  n = 0
+// launches nothing.
+constexpr int kTonebankMaxC = 256;
+constexpr int kTonebankMinB = 64;
+constexpr int kTonebankMaxB = 16384;
+constexpr int kTonebankMinF = 2;
+constexpr int kTonebankMaxF = 64;
+constexpr int kTonebankMaxHold = 64;
+constexpr int kTonebankSat = kTonebankMaxHold + 1;
+int tonebank_tile(int B);                                   // columns (row, block pairs) per workgroup of k_tonebank_power
+void tonebank_pack(int F, int B, const float* tc, const float* ts, std::vector<float>& out);
+struct TonebankCall {
+    const float* x;
+    const float* hist;
+    float* hist_out;
+    const float* tab;
+    size_t n, ldx, fill, nblocks, ldp, ldt, ldo, ldy;
+    int C, B, F, hold;
+    float floor;
+    double dominance;
+    const int8_t* want;
+    const int* since;
+    int* since_out;
+    float* power;
+    int8_t* tone;
+    uint8_t* open;
+    float* y;
+};
+void tonebank(const TonebankCall& c, hipStream_t s);
 // k_stbank.hip: FM stereo decoder over bank rows (StereoBank).  C <= kStbankMaxC
 // rows of float32 multiplex, row c's n samples at x + c * ldx; decimation
 // 1 <= D <= kStbankMaxD, two real prototypes of L <= kStbankMaxL taps.  hist /

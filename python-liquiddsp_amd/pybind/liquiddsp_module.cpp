@@ -94,21 +94,24 @@ T get_value(G get, const Q& q)
 }
 
 // The element kinds of inputs and results
-enum class Kind { f32, c64, i16, u8, i32 };
+enum class Kind { f32, c64, i16, u8, i32, i8 };
 constexpr Kind kind_of(bool cplx) { return cplx ? Kind::c64 : Kind::f32; }
 const char* torch_name(Kind k)
 {
     if (k == Kind::i32) return "int32";
+    if (k == Kind::i8) return "int8";
     return k == Kind::c64 ? "complex64" : (k == Kind::f32 ? "float32" : (k == Kind::i16 ? "int16" : "uint8"));
 }
 size_t kind_size(Kind k)
 {
     if (k == Kind::i32) return 4;
+    if (k == Kind::i8) return 1;
     return k == Kind::c64 ? 8 : (k == Kind::f32 ? 4 : (k == Kind::i16 ? 2 : 1));
 }
 py::dtype np_dtype(Kind k)
 {
     if (k == Kind::i32) return py::dtype::of<int32_t>();
+    if (k == Kind::i8) return py::dtype::of<int8_t>();
     return k == Kind::c64 ? py::dtype::of<cf>()
                           : (k == Kind::f32 ? py::dtype::of<float>()
                                             : (k == Kind::i16 ? py::dtype::of<int16_t>() : py::dtype::of<uint8_t>()));
@@ -1343,6 +1346,119 @@ struct AGCBank {
     }
 };
 
+// ------------------------------------------------------------------ ToneBank (no reference counterpart)
+// Per-row tone detector and tone squelch over bank rows (ldsp.h): float32[nchan, K]
+// (input as the AudioBank's: a bank's output is read in place) -> the gated rows
+// or (tone, power).  tone, power and open keep the last call's.
+struct ToneBank {
+    Handle<ldsp_tonebank_t, ldsp_tonebank_destroy> q;
+    unsigned C = 0, F = 0, B = 0, hold = 0;
+    int window = 0;
+    py::object last_tone = py::none(), last_power = py::none(), last_open = py::none();
+    static std::vector<int> to_ivec(const py::object& o, const char* what)
+    {
+        const std::vector<double> d = SquelchBank::to_dvec(o);
+        std::vector<int> v(d.size());
+        for (size_t i = 0; i < d.size(); i++) {
+            if (!(d[i] >= -1.0 && d[i] <= 64.0) || d[i] != std::floor(d[i])) throw py::value_error(what);
+            v[i] = (int)d[i];
+        }
+        return v;
+    }
+    ToneBank(int nchan, const py::object& tones, int block, const std::string& win, double dominance, float floor_,
+             int hold_, const py::object& want)
+    {
+        if (nchan < 0) throw py::value_error("ToneBank: nchan must lie in 1 .. 256");
+        if (block < 0) throw py::value_error("ToneBank: block must be a multiple of 64 in 64 .. 16384");
+        if (hold_ < 0) throw py::value_error("ToneBank: hold must lie in 0 .. 64");
+        if (win != "hann" && win != "rect") throw py::value_error("ToneBank: window must be 'hann' or 'rect'");
+        const std::vector<double> f = SquelchBank::to_dvec(tones);
+        check(ldsp_tonebank_create((unsigned)nchan, f.data(), (unsigned)f.size(), (unsigned)block,
+                                   win == "hann" ? LDSP_TONE_HANN : LDSP_TONE_RECT, dominance, floor_, (unsigned)hold_,
+                                   q.out()));
+        check(ldsp_tonebank_get_info(q, &C, &F, &B, &window, &hold, nullptr));
+        if (!want.is_none()) set_want(want);
+    }
+    void reset() { check(ldsp_tonebank_reset(q)); }
+    py::array_t<double> tones()
+    {
+        py::array_t<double> f(F);
+        check(ldsp_tonebank_get_tables(q, f.mutable_data(), nullptr, nullptr, nullptr));
+        return f;
+    }
+    py::array_t<float> tables()
+    {
+        py::array_t<float> t({(py::ssize_t)2, (py::ssize_t)F, (py::ssize_t)B});
+        check(ldsp_tonebank_get_tables(q, nullptr, t.mutable_data(), t.mutable_data() + (size_t)F * B, nullptr));
+        return t;
+    }
+    double sumw()
+    {
+        double s;
+        check(ldsp_tonebank_get_tables(q, nullptr, nullptr, nullptr, &s));
+        return s;
+    }
+    py::array_t<int> get_want()
+    {
+        py::array_t<int> w(C);
+        check(ldsp_tonebank_get_want(q, w.mutable_data()));
+        return w;
+    }
+    void set_want(const py::object& o)
+    {
+        const std::vector<int> w = to_ivec(o, "ToneBank: want must be integers in -1 .. F - 1");
+        check(ldsp_tonebank_set_want(q, w.data(), (unsigned)w.size()));
+    }
+    double get_dominance() { return get_value<double>(ldsp_tonebank_get_dominance, q); }
+    void set_dominance(double d) { check(ldsp_tonebank_set_dominance(q, d)); }
+    float get_floor() { return get_value<float>(ldsp_tonebank_get_floor, q); }
+    void set_floor(float f) { check(ldsp_tonebank_set_floor(q, f)); }
+    unsigned fill()
+    {
+        unsigned f;
+        check(ldsp_tonebank_get_info(q, nullptr, nullptr, nullptr, nullptr, nullptr, &f));
+        return f;
+    }
+    size_t tile()
+    {
+        size_t t;
+        check(ldsp_debug_tonebank_tile(B, &t));
+        return t;
+    }
+    size_t num_outputs(size_t K)
+    {
+        size_t n;
+        check(ldsp_tonebank_num_outputs(q, K, &n));
+        return n;
+    }
+    py::array_t<int> state()
+    {
+        py::array_t<int> s(C);
+        check(ldsp_tonebank_get_state(q, s.mutable_data()));
+        return s;
+    }
+    // tone, power, open and (gate) the gated rows of the call's whole blocks
+    py::object run(const py::handle& x, bool gate)
+    {
+        const CallIn in = in_rows(x, Kind::f32, C, "ToneBank", true, Strided::refuse);
+        size_t N = 0, nw = 0;
+        check(ldsp_tonebank_num_outputs(q, in.n, &N));
+        CallOut tn = make_out(in, Kind::i8, C, (py::ssize_t)N), op = make_out(in, Kind::u8, C, (py::ssize_t)N), y;
+        CallOut pw = make_out(in, Kind::f32, (size_t)C * N, (py::ssize_t)F);
+        if (gate) y = make_out(in, Kind::f32, C, (py::ssize_t)(N * B));
+        invoke(in, [&](int mem, void* s) {
+            return ldsp_tonebank_execute(q, (const float*)in.ptr, in.ld, in.n, (float*)pw.ptr, N * F, (int8_t*)tn.ptr, N,
+                                         (uint8_t*)op.ptr, N, (float*)y.ptr, N * B, &nw, mem, s);
+        });
+        last_tone = tn.obj;
+        last_power = pw.obj.attr("reshape")(py::make_tuple(C, N, F));
+        last_open = op.obj;
+        return gate ? y.obj : py::object(py::make_tuple(last_tone, last_power));
+    }
+    py::object call(const py::handle& x) { return run(x, true); }
+    py::object measure(const py::handle& x) { return run(x, false); }
+};
+
 // ------------------------------------------------------------------ StereoBank (no reference counterpart; FMStereo is another decoder)
 // Feed-forward FM stereo decoder over bank rows (ldsp.h): float32[nchan, K] of
 // multiplex -> float32[nchan, 2, ncols], left at [:, 0] and right at [:, 1]; its
@@ -2511,6 +2627,44 @@ PYBIND11_MODULE(_liquiddsp, m)
         .def_property_readonly("gain_db", &AGCBank::gain_db, "gain_q in dB, float32")
         .def("__call__", &AGCBank::call,
              "float32 or complex64 [nchan, K] -> the same kind [nchan, emitted * block]: the stream one block behind");
+
+    // ---- ToneBank (beyond the reference: per-row tone detector and tone squelch over bank rows)
+    py::class_<ToneBank>(m, "ToneBank")
+        .def(py::init<int, py::object, int, std::string, double, float, int, py::object>(), py::arg("nchan"),
+             py::arg("tones"), py::arg("block") = 4096, py::arg("window") = "hann", py::arg("dominance") = 8.0,
+             py::arg("floor") = 0.0f, py::arg("hold") = 1, py::arg("want") = py::none())
+        .def("reset", &ToneBank::reset, "the initial state; the settings stay")
+        .def("num_outputs", &ToneBank::num_outputs, py::arg("K"),
+             "blocks the next call returns for K input samples per row")
+        .def_property_readonly("nchan", [](ToneBank& c) { return c.C; })
+        .def_property_readonly("ntones", [](ToneBank& c) { return c.F; })
+        .def_property_readonly("block", [](ToneBank& c) { return c.B; })
+        .def_property_readonly("hold", [](ToneBank& c) { return c.hold; }, "in blocks")
+        .def_property_readonly("window", [](ToneBank& c) { return c.window == LDSP_TONE_HANN ? "hann" : "rect"; })
+        .def_property_readonly("tones", &ToneBank::tones, "cycles per row sample")
+        .def_property_readonly("tables", &ToneBank::tables,
+                               "float32[2, ntones, block]: the cosine and sine tables, window and scale folded in")
+        .def_property_readonly("window_sum", &ToneBank::sumw, "sum of the window, float64")
+        .def_property("want", &ToneBank::get_want, &ToneBank::set_want,
+                      "the tone that opens each row, -1 for any; set with a scalar or nchan values, from the next block on")
+        .def_property("dominance", &ToneBank::get_dominance, &ToneBank::set_dominance,
+                      "the best power over the mean of the others; from the next block on")
+        .def_property("floor", &ToneBank::get_floor, &ToneBank::set_floor,
+                      "the power the best tone must exceed; from the next block on")
+        .def_property_readonly("fill", &ToneBank::fill, "samples per row carried to the next call")
+        .def_property_readonly("tile", &ToneBank::tile, "columns (row, block pairs) per workgroup of the power kernel")
+        .def_property_readonly("tone", [](ToneBank& c) { return c.last_tone; },
+                               "the last call's int8[nchan, nblocks]: the dominant tone or -1; None before the first")
+        .def_property_readonly("power", [](ToneBank& c) { return c.last_power; },
+                               "the last call's float32[nchan, nblocks, ntones]; None before the first")
+        .def_property_readonly("open", [](ToneBank& c) { return c.last_open; },
+                               "the last call's uint8[nchan, nblocks], 1 where the gate is open; None before the first")
+        .def_property_readonly("state", &ToneBank::state,
+                               "blocks since the last accepted one per row after the last call (65: none within reach)")
+        .def("measure", &ToneBank::measure, py::arg("x"),
+             "float32[nchan, K] -> (tone, power); advances the stream, writes no rows")
+        .def("__call__", &ToneBank::call,
+             "float32[nchan, K] -> float32[nchan, nblocks * block]: the stream's whole blocks, closed ones zeroed");
 
     // ---- StereoBank (beyond the reference: feed-forward FM stereo decoder over bank rows)
     py::class_<StereoBank>(m, "StereoBank")
