@@ -95,9 +95,11 @@ def test_parity_special_frequencies_one_tuner_each(ld):
 
 
 # ---------------------------------------------------------------- 2. user taps
-@pytest.mark.parametrize("D,L", [(8, 3), (4, 37), (64, 17 * 64)])
+@pytest.mark.parametrize("D,L", [(8, 3), (4, 37), (64, 17 * 64), (8, 1), (8, 2), (8, 7), (8, 9), (32, 5)])
 def test_user_taps_against_definition(ld, D, L):
-    """A prototype shorter than D, one that ends inside a phase and the longest supported."""
+    """A prototype shorter than D, one that ends inside a phase and the longest supported; then those around
+    the eight waves' parts of ceil(L / 8): no history and seven idle waves, two taps, one tap in each of seven
+    waves, parts of two with the last three waves idle, and L far below the largest D of the bank demodulators."""
     rng = np.random.default_rng(1500 + L)
     h = (rng.standard_normal(L) / np.sqrt(L)).astype(np.float32)
     dc = ld.Downconverter(freqs_for(rng, 5), D, taps=h)

@@ -103,9 +103,10 @@ def test_parity_with_definition(ld, ora, C, D, m):
     assert err.max() <= GATE, (int(np.argmax(err)), float(err.max()))
 
 
-@pytest.mark.parametrize("D,L", [(8, 3), (4, 37), (64, 17 * 64)])
+@pytest.mark.parametrize("D,L", [(8, 3), (4, 37), (64, 17 * 64), (8, 1), (8, 2), (1, 4), (32, 5)])
 def test_user_taps_against_definition(ld, ora, D, L):
-    """A prototype shorter than D, one that ends inside a phase and the longest supported."""
+    """A prototype shorter than D, one that ends inside a phase and the longest supported; then one tap (no
+    history), two, a prototype at decimation 1 and one far shorter than a large D."""
     rng = np.random.default_rng(1500 + L)
     h = (rng.standard_normal(L) / np.sqrt(L)).astype(np.float32)
     fb = ld.FMBank(5, KF, D, taps=h)

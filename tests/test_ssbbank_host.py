@@ -23,6 +23,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from bank_prototypes import row_taps
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 PKG = os.path.join(REPO, "python-liquiddsp_amd")
@@ -104,20 +106,6 @@ def designed(ora, L, fc, As):
 def word(bfo):
     """rint(bfo 2^32) mod 2^32 in exact integer arithmetic (the product is exact; round-half-even)."""
     return int(np.rint(np.float64(bfo) * 4294967296.0)) % (1 << 32)
-
-
-def row_taps(p, lo, hi, words, sides):
-    """g_c[j] = p[j] exp(2 pi i psi_c[j] / 2^33) with psi in Python integers, double, rounded once."""
-    L = len(p)
-    wm = int(np.rint(np.float64((lo + hi) / 2) * 4294967296.0))
-    g = np.empty((len(words), L), np.complex64)
-    for c, (w, s) in enumerate(zip(words, sides)):
-        psi = np.array([(s * wm * (2 * j - (L - 1)) + 2 * j * int(w)) % (1 << 33) for j in range(L)], dtype=np.int64)
-        psi = np.where(psi >= 1 << 32, psi - (1 << 33), psi)               # signed: exact in double
-        a = np.pi * (psi.astype(np.float64) / 4294967296.0)
-        pd = np.asarray(p, np.float32).astype(np.float64)
-        g[c] = ((pd * np.cos(a)).astype(np.float32) + 1j * (pd * np.sin(a)).astype(np.float32)).astype(np.complex64)
-    return g
 
 
 def ulps(a, b):
@@ -224,6 +212,10 @@ def test_user_taps(ld, lib):
     sb = ld.SSBBank(2, 4, lo=0.01, hi=0.1, bfo=[0.2, -0.1], sideband=["lsb", "usb"], taps=p)
     assert sb.ntaps == 37 and (bits(sb.taps) == bits(p)).all() and (sb.lo, sb.hi) == (0.01, 0.1)
     assert ulps(sb.row_taps, row_taps(p, 0.01, 0.1, sb.words, [-1, 1])).max() <= 1
+    even = rng.standard_normal(36).astype(np.float32)  # an even length: the tap phase counts in 2^-33 turns
+    sb = ld.SSBBank(3, 4, lo=0.01, hi=0.1, bfo=[0.2, -0.1, 0.0], sideband=["lsb", "usb", "usb"], taps=even)
+    assert sb.ntaps == 36 and (bits(sb.taps) == bits(even)).all()
+    assert ulps(sb.row_taps, row_taps(even, 0.01, 0.1, sb.words, [-1, 1, 1])).max() <= 1
     one = ld.SSBBank(1, 8, lo=0.01, taps=[0.5])       # L = 1: psi = 0, g = p
     assert one.ntaps == 1 and one.row_taps[0, 0] == 0.5 and one.hi == 0.0625 - 0.01
     ld.SSBBank(1, 1, taps=np.ones(1025, np.float32))  # the longest
